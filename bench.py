@@ -16,14 +16,22 @@ ONCE over RCCL (xGMI); each rank converts it to the Fourier domain on its own GP
 its shard -- no collective in the timed loop except the bracketing barriers.  value = sum of PBS
 over ranks / max wall time over ranks.
 
-The JSON line also carries the roofline of the dominant kernel (FP64-VALU bound; its duration from
-the engine's per-kernel HIP-event timer on the launch stream -- DESIGN.md 6), the measured traffic
-and issue counters of that same kernel from the committed per-kernel rocprofv3 PMC summaries
-(profiles/r03_pmc_*.json), the rates of the host-pointer C ABI (PCIe-inclusive, and the
-reference's one-ciphertext-per-call pattern from native threads; never `value`) and the CPU
-baseline (oracle C restatement, 1 PBS per thread on the host's CPU share, rank 0, N = 1 only).
-The default run also measures the other BASELINE configurations (`other_workloads`), at N > 1
-on every rank of the job.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: keys,
+W warm-up steps, K timed steps, the decryption check, and the JSON line with the roofline of the
+dominant kernel (FP64-VALU bound; its duration from the engine's per-kernel HIP-event timer on
+the launch stream during the timed steps -- DESIGN.md 6 -- and the traffic and issue counters of
+that same kernel from the committed per-kernel rocprofv3 PMC summaries, profiles/r03_pmc_*.json).
+
+`--full` adds every side measurement, each a run of its own after or beside the timed steps: the
+rates of the host-pointer C ABI (PCIe-inclusive, and the reference's one-ciphertext-per-call
+pattern from native threads; never `value`), the one-call latency, the CPU baseline (oracle C
+restatement, 1 PBS per thread on the host's CPU share, rank 0, N = 1 only) and, without `--params`,
+the other BASELINE configurations (`other_workloads`), at N > 1 on every rank of the job.  The
+`--no-*` options switch single legs of a `--full` run off.
+
+`--dump-outputs DIR` writes what the last timed step left in the caller's output buffer as
+DIR/<name>.npy (float64, exact: see dump_u64), so that two builds can be compared output for
+output; keys, messages and encryptions depend only on `--seed`.
 
 `--launch-selftest` runs the rank/shard/aggregation code with a stub step on the CPU (gloo), so
 that the multi-rank path is testable without a GPU (tests/test_bench_launch.py).
@@ -521,7 +529,7 @@ def launch_ranks(args) -> int:
     return subprocess.call(cmd, env=env)
 
 
-# The other BASELINE configurations measured beside the headline by the default run:
+# The other BASELINE configurations measured beside the headline by a --full run without --params:
 # (entry name, --params, extra options).  `4_4_full` is config 3 at its stated size (65,536
 # ciphertexts in one call, a GLOBAL batch: split over the ranks at N > 1, i.e. strong scaling for
 # that entry), warmed up on its first 1024 ciphertexts.
@@ -603,7 +611,7 @@ def compact_summary(line: dict) -> dict:
 
 
 def _child_args(args, params, opts) -> list:
-    a = ["--params", params, "--steps", str(opts["steps"]), "--warmup", str(opts.get("warmup", 1)),
+    a = ["--full", "--params", params, "--steps", str(opts["steps"]), "--warmup", str(opts.get("warmup", 1)),
          "--no-cpu-baseline", "--seed", str(args.seed)]
     a += ["--callers-only"] if opts.get("callers") else ["--no-host-abi"]
     if opts.get("global_batch"):
@@ -615,7 +623,7 @@ def _child_args(args, params, opts) -> list:
 
 def other_workloads(args) -> dict:
     """N = 1: the other configurations, each run once as a child `bench.py --params X` BEFORE this
-    process touches the GPU, so the default run also measures them under the caller's clock;
+    process touches the GPU, so that run also measures them under the caller's clock;
     summarised into the headline line (the headline value stays the 2_2 PBS rate).  A failed
     child is reported, not fatal."""
     res = {}
@@ -726,6 +734,7 @@ def other_workloads_ranks(args, R, runner, emit=None) -> dict:
         a.warmup_batch = opts.get("warmup_batch", 0)
         a.batch = args.batch if args.launch_selftest else 0
         a.other = None
+        a.dump_outputs = None  # the headline's outputs only
         t = time.perf_counter()
 
         def over_budget(name=name, t=t):
@@ -895,8 +904,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=0, help="ciphertexts per GPU per step (default 4096; 1024 at 4_4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-abi", action="store_true", help="skip the host-pointer ABI rate")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: host-pointer ABI rates, one-call latency, CPU baseline "
+                         "and (without --params) the other configurations; off: the headline's steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-host-abi", action="store_true", help="--full: skip the host-pointer ABI rate")
     ap.add_argument("--callers-only", action="store_true",
                     help="host-pointer ABI: only the one-ciphertext-per-call leg (1 / 64 / 256 callers, 1 x 256 "
                          "submitted), not the batched pageable / pinned rates")
@@ -905,7 +919,7 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default run only: skip the other configurations measured beside the headline")
+                    help="--full without --params: skip the other configurations measured beside the headline")
     ap.add_argument("--params", choices=sorted(PARAMS), default=None,
                     help="2_2 = the BASELINE metric; 2_2ks = KS+PBS; mb3/mb2 = multi-bit PBS (config 5)")
     ap.add_argument("--launch-selftest", action="store_true",
@@ -916,8 +930,10 @@ def main():
                     help="warm-up launches use only the first N ciphertexts of the rank's batch")
     ap.add_argument("--ctx-devices", default=None, metavar="LIST",
                     help="only the one-process multi-device context entry over the comma-separated device "
-                         "list (the default run adds it: devices 0,0 at N = 1, 0..N-1 at N > 1)")
+                         "list (the --full run without --params adds it: devices 0,0 at N = 1, 0..N-1 at N > 1)")
     args = ap.parse_args()
+    if not args.full:  # the side measurements run only under --full
+        args.no_cpu_baseline = args.no_host_abi = args.no_single_call = args.no_other_workloads = True
     if args.ctx_devices:
         print(json.dumps(ctx_devices_line(args, [int(d) for d in args.ctx_devices.split(",")])), flush=True)
         return
@@ -929,7 +945,7 @@ def main():
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={ws}; n_gpus is taken from the world that runs")
     if args.launch_selftest:
         sys.exit(run_selftest(args))
-    # the default invocation (no --params) also measures the other configurations: on one GPU as
+    # --full without --params also measures the other configurations: on one GPU as
     # child processes before this one touches the GPU, on N GPUs in-process on every rank
     default_run = args.params is None and not args.no_other_workloads
     args.other = None
@@ -979,6 +995,31 @@ def merge_other(line, res):
     if bad:
         out["other_workloads_errors"] = bad
     return out
+
+
+DUMP_ROWS = 1024        # rows of one dumped array (2 x 1024 x 2049 float64 = 34 MB at 2_2)
+DUMP_BYTES = 24 << 20   # and at most this many bytes per array (96 rows at N = 32768)
+
+
+def dump_u64(args, R, name: str, words: np.ndarray) -> dict:
+    """--dump-outputs: the u64 torus words of the last timed step's output (one ciphertext per row)
+    as DIR/<name>_hi32.npy and DIR/<name>_lo32.npy -- the upper and lower 32 bits of every word as
+    float64, so exact -- for a fixed sample of at most DUMP_ROWS rows and DUMP_BYTES per array (a
+    seeded choice that depends only on the shape; DIR/<name>_rows.npy holds the sampled row
+    numbers).  With more than one rank every rank writes its shard's sample as <name>_rank<r>_*."""
+    w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, words.shape[-1])
+    n = w.shape[0]
+    keep = max(1, min(DUMP_ROWS, DUMP_BYTES // (8 * w.shape[1])))
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(20240).choice(n, keep, replace=False))
+    w = w[rows]
+    if R.world > 1:
+        name = f"{name}_rank{R.rank}"
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, f"{name}_hi32.npy"), (w >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(args.dump_outputs, f"{name}_lo32.npy"), (w & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(args.dump_outputs, f"{name}_rows.npy"), rows.astype(np.float64))
+    return {"dir": args.dump_outputs, "arrays": [f"{name}_hi32", f"{name}_lo32", f"{name}_rows"],
+            "rows": int(rows.size), "of": int(n), "words_per_row": int(w.shape[1])}
 
 
 def run_workload(args, R) -> dict | None:
@@ -1347,6 +1388,7 @@ def run_pbs(args, P, pname, workload, kname, R):
     eng.kernel_timing(0)
 
     out = d_out.cpu().numpy().view(np.uint64)
+    dumped = dump_u64(args, R, "pbs_out", out) if args.dump_outputs else None
     dec = client.decode(client.lwe_decrypt(glwe_sk, out), P.delta) % np.uint64(msg_space)
     ok = int(np.count_nonzero(dec == msgs))
     agg = aggregate(R, nb * args.steps, wall, ok, nb, lo, hi)
@@ -1399,6 +1441,8 @@ def run_pbs(args, P, pname, workload, kname, R):
             "check": {"decrypted_ok": agg["ok"], "of": agg["of"]},
             "setup": setup,
         }
+        if dumped:
+            line["dump_outputs"] = dumped
         if host_abi:
             line["host_abi"] = host_abi
         if latency:
@@ -1481,6 +1525,8 @@ def run_mul32(args, P, workload, kname, R):
     step_ms = float(np.mean([s.elapsed_time(e) for s, e in evs]))
     ok = int(np.count_nonzero(cks.decrypt(out) == (a * b) % np.uint64(1 << 32)))
     agg = aggregate(R, (hi - lo) * args.steps, wall, ok, hi - lo, lo, hi)
+    # one row per radix block of the products, as the caller's host copy holds them
+    dumped = dump_u64(args, R, "mul32_out", sks.to_host(out).data) if args.dump_outputs else None
     latency = None
     if R.rank == 0 and not args.no_single_call:
         # ONE multiply (the reference's published FheUint32 `*`: 333 ms on a 128-vCPU m6i.metal,
@@ -1554,6 +1600,8 @@ def run_mul32(args, P, workload, kname, R):
             "check": {"decrypted_ok": agg["ok"], "of": agg["of"]},
             "setup": {"keygen_s": t_gen, "bsk_broadcast_s": t_bc, "ksk_broadcast_s": t_bc_ksk},
         }
+        if dumped:
+            line["dump_outputs"] = dumped
         if latency:
             line["single_call_latency_ms"] = latency["ms"]
             line["single_call_latency"] = latency

@@ -29,9 +29,9 @@ for s in ${STAGES:-tests smoke bench}; do
     tests) step r06_gpu_tests 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     t) step r06_tests_${T_NAME:-sel} 600 python -u -m pytest $T_FILES -m gpu -x -v --timeout 120 --timeout-method thread ;;
     smoke) step r06_smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step r06_bench_default${BENCH_SUFFIX} 900 python bench.py --steps 10 --warmup 2 ;;
+    bench) step r06_bench_default${BENCH_SUFFIX} 900 python bench.py --full --steps 10 --warmup 2 ;;
     ctx) step r06_ctx_devices 500 python bench.py --ctx-devices ${CTX_DEVS:-0,0} --steps 3 --warmup 1 ;;
-    rehearse2) step r06_rehearse2_gloo_1gpu 1100 env BENCH_DIST_BACKEND=gloo python -u bench.py --gpus 2 --steps 5 --warmup 1 ;;
+    rehearse2) step r06_rehearse2_gloo_1gpu 1100 env BENCH_DIST_BACKEND=gloo python -u bench.py --full --gpus 2 --steps 5 --warmup 1 ;;
     ab) for pass in 1 2; do
           for t in ${AB_TAGS:-3_3}; do
             TFHE_MI355_LIB=$AB_LIB bline $t r06_ab_${AB_NAME}_${t}_old$pass ${AB_ARGS}

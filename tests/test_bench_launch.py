@@ -53,9 +53,9 @@ def test_gpus_mismatch_with_world_is_an_error():
 
 
 @pytest.mark.timeout(180)
-def test_other_workloads_failed_child_is_reported_not_fatal(monkeypatch):
-    """The default run's side measurements (other_workloads): a child that cannot run (no GPU
-    here) is reported as an error entry with its wall time; the caller keeps going."""
+def test_other_workloads_failed_child_is_reported_not_fatal(monkeypatch, tmp_path):
+    """The `--full` run's side measurements (other_workloads): a child that cannot run (no engine
+    library, no visible GPU) is reported as an error entry with its wall time; the caller keeps going."""
     import argparse
     import importlib.util
 
@@ -63,7 +63,10 @@ def test_other_workloads_failed_child_is_reported_not_fatal(monkeypatch):
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
     monkeypatch.setattr(bench, "OTHER_WORKLOADS", (("2_2ks", "2_2ks", {"steps": 1}),))
-    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")  # the child must fail fast on this CPU box
+    # the child must fail fast with or without a GPU in the machine: no visible device, and no engine
+    # library to load (HIP on its own does not honour CUDA_VISIBLE_DEVICES everywhere)
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("TFHE_MI355_LIB", str(tmp_path / "no_such_libtfhe_mi355.so"))
     res = bench.other_workloads(argparse.Namespace(seed=1))
     assert set(res) == {"2_2ks", "ctx_devices"}  # ctx_devices: the one-process multi-device entry, always run
     for k in res:
@@ -72,11 +75,11 @@ def test_other_workloads_failed_child_is_reported_not_fatal(monkeypatch):
 
 @pytest.mark.timeout(240)
 def test_multi_rank_default_run_merges_every_configuration():
-    """The driver's N > 1 default run: every rank runs each other configuration in-process on the
-    job's process group (keys broadcast, shards, barrier-bracketed timing, max wall over ranks)
+    """The driver's N > 1 `--full` run without `--params`: every rank runs each other configuration
+    in-process on the job's process group (keys broadcast, shards, barrier-bracketed timing, max wall over ranks)
     before the headline, and rank 0 prints ONE line whose other_workloads entries carry the world
     size they ran at (stub steps on gloo here; on the GPU box these are the PBS workloads)."""
-    p, lines = _run(["--gpus", "2", "--launch-selftest", "--steps", "2", "--warmup", "1", "--batch", "8"])
+    p, lines = _run(["--full", "--gpus", "2", "--launch-selftest", "--steps", "2", "--warmup", "1", "--batch", "8"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, p.stdout
     d = json.loads(lines[0])
@@ -101,13 +104,27 @@ def test_multi_rank_default_run_merges_every_configuration():
     assert d["world_size"] == 2 and d["check"]["decrypted_ok"] == 16
 
 
+@pytest.mark.timeout(180)
+def test_plain_run_measures_the_headline_only():
+    """Without `--full` the same invocation times the headline's steps and nothing else: `--steps` is
+    the number of timed steps, `ms_per_step` their mean wall time, no other_workloads entry."""
+    p, lines = _run(["--gpus", "2", "--launch-selftest", "--steps", "4", "--warmup", "1", "--batch", "8"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert "other_workloads" not in d and "summary" not in d
+    assert d["steps"] == 4 and d["units_total"] == 16 * 4
+    assert abs(d["ms_per_step"] - d["wall_max_s"] / 4 * 1e3) < 1e-6
+    assert d["ms_per_step"] >= 0.02 * 2 * 1e3   # the slower rank's stub step
+
+
 @pytest.mark.timeout(240)
 def test_multi_rank_workload_over_budget_still_prints_the_line():
-    """N > 1: one configuration stalls (stub sleeping far past BENCH_WORKLOAD_BUDGET_S): every
+    """N > 1, `--full`: one configuration stalls (stub sleeping far past BENCH_WORKLOAD_BUDGET_S): every
     rank's watchdog fires, rank 0 prints the merged line -- the headline (measured first), the
     configurations measured before the stall, and that entry marked as an error -- and the job
     exits non-zero instead of hanging the multi-GPU run."""
-    p, lines = _run(["--gpus", "2", "--launch-selftest", "--steps", "2", "--warmup", "1", "--batch", "8"],
+    p, lines = _run(["--full", "--gpus", "2", "--launch-selftest", "--steps", "2", "--warmup", "1", "--batch", "8"],
                     extra_env={"BENCH_SELFTEST_STALL": "mb2", "BENCH_WORKLOAD_BUDGET_S": "4"})
     assert p.returncode != 0
     assert len(lines) == 1, p.stdout

@@ -74,11 +74,35 @@ def test_split_chunk_matches_the_engine_rule():
 
 
 def test_mall_ceiling_is_the_committed_probe():
-    txt = open(os.path.join(ROOT, "profiles", "r03_mall_stream_probe.log")).read()
+    # the probe's recorded output (scripts/probes/mall_stream_probe.hip), stored with the test vectors
+    txt = open(os.path.join(ROOT, "tests", "golden", "mall_stream_probe.txt")).read()
     # working sets of 96-255 MiB: past the 32 MiB of L2, inside the 256 MiB Infinity Cache
     best = max(float(l.split(": ")[1].split(" TB/s")[0]) for l in txt.splitlines() if "TB/s" in l and "MiB x3" in l
                and 96 <= int(l.split("working set ")[1].split(" MiB")[0]) <= 255)
     assert abs(best * 1000 - bench.MALL_STREAM_GBS) < 50
+
+
+@pytest.mark.parametrize("n", [5, bench.DUMP_ROWS + 7])
+def test_dump_u64_is_exact_and_the_sample_is_fixed(tmp_path, n):
+    """--dump-outputs: float64 halves that rebuild every sampled u64 word exactly; the same rows on
+    every call; at most DUMP_ROWS of them."""
+    import argparse
+
+    import numpy as np
+
+    words = np.random.default_rng(3).integers(0, 2 ** 64, (n, 9), dtype=np.uint64)
+    words[0, 0], words[0, 1] = np.uint64(2 ** 64 - 1), np.uint64(0)
+    R = argparse.Namespace(world=1, rank=0)
+    info = [bench.dump_u64(argparse.Namespace(dump_outputs=str(tmp_path / d)), R, "x", words) for d in ("a", "b")]
+    assert info[0]["rows"] == min(n, bench.DUMP_ROWS) and info[0]["of"] == n
+    a, b = ({k: np.load(tmp_path / d / f"x_{k}.npy") for k in ("hi32", "lo32", "rows")} for d in ("a", "b"))
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k])
+    rows = a["rows"].astype(np.int64)
+    assert len(set(rows)) == rows.size and (np.diff(rows) > 0).all()
+    back = (a["hi32"].astype(np.uint64) << np.uint64(32)) | a["lo32"].astype(np.uint64)
+    assert np.array_equal(back, words[rows])
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
 
 
 def test_compact_summary_keeps_every_workload_and_the_callers():
