@@ -30,7 +30,8 @@ def main():
             if "." not in e.split("_")[-1]:
                 pats.add(e + "*")  # a stem: every extension
     files = sorted(os.listdir(os.path.join(ROOT, "profiles")))
-    unc = [f for f in files if not any(fnmatch.fnmatch(f, p) or f.startswith(p.rstrip("*") + ".") for p in pats)]
+    unc = [f for f in files if ("profiles/" + f) not in text  # a name without a round prefix, written in full
+           and not any(fnmatch.fnmatch(f, p) or f.startswith(p.rstrip("*") + ".") for p in pats)]
     for f in unc:
         print(f)
     print(f"{len(unc)} of {len(files)} profiles/ files not named", file=sys.stderr)

@@ -858,5 +858,14 @@ __device__ __forceinline__ void backward_add(cx z, cx ws, uint64_t &c_re, uint64
     torus_add_frac(c_re, mr - rint(mr), k32);
     torus_add_frac(c_im, mi - rint(mi), k32);
 }
+// same, subtracted in place (a caller that holds -c: pbs_classic.hip).  The subtrahend is the
+// increment of backward_add exactly: rint(m) - m = -(m - rint(m)), and frac_to_torus is odd
+// (rint is odd; fr = +-1/2 both give 2^63), so adding X(-fr) subtracts X(fr) mod 2^64.
+__device__ __forceinline__ void backward_sub(cx z, cx ws, uint64_t &c_re, uint64_t &c_im, double k32) {
+    double mr = fma(z.re, ws.re, z.im * ws.im);
+    double mi = fma(-z.re, ws.im, z.im * ws.re);
+    torus_add_frac(c_re, rint(mr) - mr, k32);
+    torus_add_frac(c_im, rint(mi) - mi, k32);
+}
 
 }  // namespace tfhe_mi355

@@ -13,8 +13,9 @@
 //
 // Design: a workgroup bootstraps CPW ciphertexts (4 at 2_2, else 1), one wavefront
 // per GLWE polynomial ((k+1) waves per ciphertext).  Each wave keeps its accumulator polynomial in
-// registers (u64), rotates it through its LDS buffer, decomposes and forward-FFTs it (row r = its
-// polynomial); the (k+1) row spectra of a ciphertext are published to LDS and wave c computes
+// registers (u64, held negated: rot_mask.h), rotates it through its LDS buffer, decomposes and
+// forward-FFTs it (row r = its polynomial); the (k+1) row spectra of a ciphertext are published to
+// LDS and wave c computes
 // output column c = sum_r F_r * GGSW[r][c] (GGSW streamed from L2/MALL, 16 B per lane, coalesced;
 // MAC operands read back from LDS at N = 2048 and 1024), inverse-FFTs it and adds it back.  FFT
 // twiddles and the twist live in LDS.  At 2_2: 2 waves per SIMD (<= 256 VGPRs, 244 used), LDS
@@ -30,6 +31,7 @@
 // unchanged.
 #include "engine.h"
 #include "pbs_common.h"
+#include "rot_mask.h"
 
 #ifndef CLASSIC_DIGIT2
 #define CLASSIC_DIGIT2 1  // L = 2 shapes: Digit2 (pbs_common.h) instead of the per-level digit loop (0: A/B)
@@ -45,6 +47,12 @@ namespace tfhe_mi355 {
 #endif
 #ifndef PBS_GGSW_LDS
 #define PBS_GGSW_LDS 0  // measured 2% slower than streaming from L2 (CPW=2 couples 4 waves); kept as an option
+#endif
+#ifndef PBS_ROT_GROUP
+#define PBS_ROT_GROUP 1  // L = 1: slots whose rotation gathers are issued as one group ahead of use (0: none)
+#endif
+#ifndef PBS_ROT_AHEAD
+#define PBS_ROT_AHEAD 1  // groups in flight ahead of the one being consumed
 #endif
 template <int N, int K, int L>
 struct PbsConfig {
@@ -168,10 +176,11 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
     const uint32_t li = A.lut_indexes ? min(A.lut_indexes[ct], A.lut_count - 1u) : 0u;
     const uint64_t *lut = A.luts + (size_t)li * (K + 1) * N + (size_t)wave * N;
 
-    // this wave's accumulator polynomial, in registers: c0[h] = position lane + 64 h
+    // this wave's accumulator polynomial, in registers and NEGATED (n0 = -ct0 mod 2^64, so that
+    // the rotation needs no conditional negate: rot_mask.h): n0[h] = position lane + 64 h
     // (h < V: j < M; h >= V: j = M + lane + 64 (h - V)).  ct0 = LUT / X^{b~}
     // (bootstrap.rs:255-275, polynomial_wrapping_monic_monomial_div)
-    uint64_t c0[2 * V];
+    uint64_t n0[2 * V];
     {
         const uint32_t bt = pbs_modulus_switch<LOG2N>(in[n]);
         const int full = bt / N, rem = bt % N;
@@ -180,7 +189,7 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
             const int src = lane + 64 * h + rem;
             const bool wrap = src >= N;
             uint64_t v = lut[wrap ? src - N : src];
-            c0[h] = (wrap != (bool)(full & 1)) ? 0 - v : v;
+            n0[h] = (wrap != (bool)(full & 1)) ? v : 0 - v;
         }
     }
 
@@ -247,7 +256,7 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
         if (!PBS_TSKIP_ROT) {
             wsync();
 #pragma unroll
-            for (int h = 0; h < 2 * V; h++) xb64[lane + 64 * h] = c0[h];
+            for (int h = 0; h < 2 * V; h++) xb64[lane + 64 * h] = n0[h];
             wsync();
         }
         // (X^d p)[j] = -p[N-d+j] for j < d, p[j-d] otherwise (sign flipped again when the
@@ -257,17 +266,20 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
         // per-coefficient index arithmetic); xpos may sit up to 8(N-1) bytes below xb64, which is
         // still inside LDS since the twist table (8N bytes) precedes every exchange buffer.
         const int rbase = lane - rem;  // in (-N, 64)
-        const int hcut = (63 - rbase) >> 6;
+        const int hcut = rot_hcut(lane, rem);
+        // With y = -x gathered and n0 = -c held, s x - c is one 64-bit add of y and n0 ^ (m, m),
+        // m = all ones where s = +1 (bit h of mbits: one word per CMUX and lane), xored with m
+        // afterwards (rot_mask.h; checked on the CPU by scripts/check_rot_mask.cpp)
+        const uint32_t mbits = rot_mbits(rot_wbits(hcut), full_odd);
         const uint64_t *xpos = xb64 + rbase;
         const uint64_t *xneg = xpos + N;
-        auto ct1_hi = [&](int h) -> uint32_t {
-            if (PBS_TSKIP_ROT) return (uint32_t)(c0[h] >> 32) ^ at;  // timing only: no rotation
-            const bool wrap = h < hcut;
-            const bool neg = wrap != full_odd;
-            const uint64_t x = (wrap ? xneg : xpos)[64 * h];
-            const uint64_t r = neg ? 0 - x : x;
-            return (uint32_t)((r - c0[h]) >> 32);
+        auto rot_gather = [&](int h) -> uint64_t { return (rot_wrap(hcut, h) ? xneg : xpos)[64 * h]; };
+        auto rot_finish = [&](int h, uint64_t y) -> uint32_t {
+            if (PBS_TSKIP_ROT) return (uint32_t)(n0[h] >> 32) ^ at;  // timing only: no rotation
+            const uint32_t m = rot_mask(mbits, h);
+            return rot_sum_hi(y, n0[h], m) ^ m;
         };
+        auto ct1_hi = [&](int h) -> uint32_t { return rot_finish(h, PBS_TSKIP_ROT ? 0 : rot_gather(h)); };
         uint32_t st[L > 1 ? 2 * V : 1];
         if constexpr (L == 2 && CLASSIC_DIGIT2) {
             // st[b] = level-L int16 pair of positions (b, V + b), st[V + b] = level L-1 (Digit2)
@@ -284,8 +296,40 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
 #pragma unroll 1
         for (int lvl = L; lvl >= 1; lvl--) {
             cx v[V];
+            constexpr int RG = (L == 1 && !PBS_TSKIP_ROT) ? (PBS_ROT_GROUP < V ? PBS_ROT_GROUP : V) : 0;
+            if constexpr (RG > 0) {
+                // L = 1: the gathers and twist reads of RG slots are issued PBS_ROT_AHEAD groups
+                // ahead of the digits that consume them, fenced by scheduling barriers (left to
+                // itself the scheduler pairs every gather with its use: 2V serial LDS round trips
+                // per CMUX).  Measured, DESIGN.md 5.1: one slot, one group ahead.
+                static_assert(V % RG == 0, "group size divides the slots per lane");
+                uint64_t ya[V], yb[V];
+                double2 wt[V];
+                auto issue = [&](int b0) {
 #pragma unroll
-            for (int b = 0; b < V; b++) {
+                    for (int b = b0; b < b0 + RG; b++) {
+                        ya[b] = rot_gather(b);
+                        yb[b] = rot_gather(V + b);
+                        wt[b] = s_twist[lane + 64 * b];
+                    }
+                };
+                constexpr int RA = PBS_ROT_AHEAD * RG;
+#pragma unroll
+                for (int b0 = 0; b0 < RA && b0 < V; b0 += RG) issue(b0);
+#pragma unroll
+                for (int b0 = 0; b0 < V; b0 += RG) {
+                    if (b0 + RA < V) issue(b0 + RA);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int b = b0; b < b0 + RG; b++) {
+                        const cx z = {(double)digit_l1(rot_finish(b, ya[b])), (double)digit_l1(rot_finish(V + b, yb[b]))};
+                        v[b] = cmulw(z, wt[b].x, wt[b].y);  // convert_forward_integer (x86.rs:505-596)
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+#pragma unroll
+            for (int b = RG > 0 ? V : 0; b < V; b++) {  // (no trips after the grouped form)
                 int32_t d0, d1;
                 if constexpr (L == 1) {
                     d0 = digit_l1(ct1_hi(b));
@@ -355,7 +399,7 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
                 for (int b = 0; b < V; b++) {
                     if (b % PBS_BWD_SB == 0) __builtin_amdgcn_sched_barrier(0);
                     const double2 w = s_twist[lane + 64 * b];  // the resident key carries the 1/M
-                    backward_add(v[b], cx{w.x, w.y}, c0[b], c0[V + b], k32);
+                    backward_sub(v[b], cx{w.x, w.y}, n0[b], n0[V + b], k32);
                 }
             }
         }
@@ -364,7 +408,7 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
 #pragma unroll
             for (int b = 0; b < V; b++) {
                 const double2 w = s_twist[lane + 64 * b];
-                backward_add(acc[b], cx{w.x, w.y}, c0[b], c0[V + b], k32);
+                backward_sub(acc[b], cx{w.x, w.y}, n0[b], n0[V + b], k32);
             }
         }
     }
@@ -373,21 +417,22 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
         if (active) {
             uint64_t *g = A.lwe_out + ((size_t)ct * (K + 1) + wave) * N;
 #pragma unroll
-            for (int h = 0; h < 2 * V; h++) g[lane0 + 64 * h] = c0[h];
+            for (int h = 0; h < 2 * V; h++) g[lane0 + 64 * h] = 0 - n0[h];
         }
         return;
     }
-    // sample extract at degree 0 (glwe_sample_extraction.rs:91-147)
+    // sample extract at degree 0 (glwe_sample_extraction.rs:91-147) from the negated accumulator:
+    // out[0] = acc[0] = -n0[0], out[j] = -acc[N - j] = n0[N - j]
     wsync();
 #pragma unroll
-    for (int h = 0; h < 2 * V; h++) xb64[lane0 + 64 * h] = c0[h];
+    for (int h = 0; h < 2 * V; h++) xb64[lane0 + 64 * h] = n0[h];
     wsync();
     if (active) {
         uint64_t *out = A.lwe_out + (size_t)ct * (K * N + 1);
         if (wave < K) {
-            for (int j = lane0; j < N; j += 64) out[wave * N + j] = j == 0 ? xb64[0] : 0 - xb64[N - j];
+            for (int j = lane0; j < N; j += 64) out[wave * N + j] = j == 0 ? 0 - xb64[0] : xb64[N - j];
         } else if (lane0 == 0) {
-            out[K * N] = c0[0];
+            out[K * N] = 0 - n0[0];
         }
     }
     wsync();  // the extract's reads of xb64 precede the next ciphertext's rotation writes
