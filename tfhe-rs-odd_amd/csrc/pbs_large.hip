@@ -253,9 +253,6 @@ __device__ __forceinline__ void decompose64(uint64_t x, int beta, int32_t (&d)[L
 #endif
 constexpr int TOPT = LARGE_TOPT;  // threads per top-stage workgroup
 
-#ifndef LARGE_DIGIT2
-#define LARGE_DIGIT2 1  // split / grouped digit kernels: Digit2 (pbs_common.h) when 2 base_log <= 30 (0: A/B)
-#endif
 // rotate, decompose, twist and top DIF radix-R of butterfly t of row r, CMUX i -> T.
 // G > 0 (multi-bit, step i = group i): the external product's input is the accumulator itself
 // (acc <- ExtProd(KB_i, acc), lwe_multi_bit_programmable_bootstrapping.rs:548-828): no rotation.
@@ -284,14 +281,14 @@ __device__ __forceinline__ void top_fwd_body(const LargePbsLaunch &a, int ct0, i
             ct1_pair_m<M>(acc, j, rem, full_odd, dd[0], dd[1]);
         }
         int32_t d0[L], d1[L];
-        if (LARGE_DIGIT2 && L == 2 && N <= 16384 && beta * 2 <= 30) {  // Digit2 (at N = 32768 it spilled)
+        if (L == 2 && N <= 16384 && beta * 2 <= 30) {  // Digit2 (pbs_common.h; at N = 32768 it spilled)
             uint32_t lv0, lv1;
             Digit2(beta).pair((uint32_t)(dd[0] >> 32), (uint32_t)(dd[1] >> 32), lv0, lv1);
             d0[0] = (int32_t)(int16_t)(lv0 & 0xffffu);
             d1[0] = (int32_t)(int16_t)(lv0 >> 16);
             d0[L - 1] = (int32_t)(int16_t)(lv1 & 0xffffu);
             d1[L - 1] = (int32_t)(int16_t)(lv1 >> 16);
-        } else if (LARGE_DIGIT2 && L == 1 && beta <= 30) {  // DigitL1
+        } else if (L == 1 && beta <= 30) {  // DigitL1
             const DigitL1 dl1(beta);
             d0[0] = dl1((uint32_t)(dd[0] >> 32));
             d1[0] = dl1((uint32_t)(dd[1] >> 32));
@@ -531,10 +528,10 @@ __global__ void __launch_bounds__(256) split_digits_kernel(LargePbsLaunch a, int
     for (int r = 0; r < 2; r++) {
         uint64_t dd[2];
         ct1_pair_m<M>(a.acc + ((size_t)cl * 2 + r) * N, j, rem, full_odd, dd[0], dd[1]);
-        if (LARGE_DIGIT2 && a.base_log * 2 <= 30) {  // Digit2: the same words, 32-bit
+        if (a.base_log * 2 <= 30) {  // Digit2: the same words, 32-bit
             uint32_t lv0, lv1;
             Digit2(a.base_log).pair((uint32_t)(dd[0] >> 32), (uint32_t)(dd[1] >> 32), lv0, lv1);
-            w[r] = (uint64_t)lv0 | ((uint64_t)lv1 << 32);
+            w[r] =(uint64_t)lv0 | ((uint64_t)lv1 << 32);
             continue;
         }
         int32_t d0[2], d1[2];
@@ -834,14 +831,8 @@ __global__ void __launch_bounds__((PairSubCfg<K, L>::THREADS), 2) large_pair_sub
 #ifndef MB_DIGITS_MIN
 #define MB_DIGITS_MIN 128  // smallest chunk fed packed digits (TFHE_MI355_MB_DIGITS_MIN overrides; profiles/r06_mb_digits_min.txt)
 #endif
-#ifndef MB2_PIPE
-#define MB2_PIPE 1  // phase 2's GGSW operand batches software pipelined (0: one (level, column) batch at a time)
-#endif
 #ifndef MB2_DEPTH
-#define MB2_DEPTH 2  // MB2_PIPE: operand batches issued ahead of the one being consumed (1: 11.83k / 10.16-10.28k, 2: 11.88k / 10.40-10.43k KS+PBS/s at g = 3 / 2, profiles/r05_ab_mb_depth.log)
-#endif
-#ifndef MB2_SROT
-#define MB2_SROT 1  // MAC slot of wave w rotated per workgroup (0: slot 8 h + w everywhere)
+#define MB2_DEPTH 2  // phase 2: operand batches issued ahead of the one being consumed (1: 11.83k / 10.16-10.28k, 2: 11.88k / 10.40-10.43k KS+PBS/s at g = 3 / 2, profiles/r05_ab_mb_depth.log)
 #endif
 #ifndef MB2_TSKIP
 #define MB2_TSKIP 0  // timing-only builds (wrong outputs): 1 no GGSW loads, 2 no forward sub-FFTs, 4 no
@@ -946,8 +937,8 @@ __global__ void __launch_bounds__((MbPair2Cfg<N, G>::THREADS), 2) large_mb_pair2
     const int cnt = a.chunk_count;
     if (2 * cp >= cnt) return;  // whole workgroup
     // the slot of wave w in each MAC round: 8 h + ws, rotated by the workgroup's index among those
-    // of its XCD (MB2_SROT) so that its CUs do not all stream the same GGSW slot at once
-    const int ws = (wave + (MB2_SROT ? (int)(blockIdx.x >> 3) : 0)) & 7;
+    // of its XCD so that its CUs do not all stream the same GGSW slot at once
+    const int ws = (wave + (int)(blockIdx.x >> 3)) & 7;
     double2 *s1 = lds + Cfg::S1;
     for (int e = threadIdx.x; e < SubFft::Lds::s1_len; e += Cfg::THREADS) s1[e] = a.W[R * (e & 63) * ((e >> 6) + 1)];
     const SubFft::Lds tw{s1, s1};
@@ -1039,7 +1030,6 @@ __global__ void __launch_bounds__((MbPair2Cfg<N, G>::THREADS), 2) large_mb_pair2
 #pragma unroll
         for (int sl = 0; sl < 8; sl++) *hslot(c1, p1, sl) = make_double2(v[8 * h + sl].re, v[8 * h + sl].im);
         const int s = 8 * h + ws;  // this wave's slot in round h (wave-uniform)
-#if MB2_PIPE
         // the round's 8 operand batches (level, column, row) of 2^g GGSW values each, software
         // pipelined: batch k + 1 in flight while batch k is consumed (the same registers as one
         // (level, column) batch); batch 0 is issued before the barrier
@@ -1056,7 +1046,6 @@ __global__ void __launch_bounds__((MbPair2Cfg<N, G>::THREADS), 2) large_mb_pair2
         double2 gb[NB][NSEL];
 #pragma unroll
         for (int st = 0; st < MB2_DEPTH; st++) gload(st, gb[st]);
-#endif
         __syncthreads();  // (h = 0: also the twist planes)
         const uint32_t f = fl + (uint32_t)R * SubFft::freq_slot(s);
         cx mono[CPW][NSEL];
@@ -1064,7 +1053,6 @@ __global__ void __launch_bounds__((MbPair2Cfg<N, G>::THREADS), 2) large_mb_pair2
         for (int c = 0; c < CPW; c++)
 #pragma unroll
             for (int sel = 1; sel < NSEL; sel++) mono[c][sel] = Tw::mono(deg[c][sel] - 4u * deg[c][sel] * f);
-#if MB2_PIPE
         cx ff[CPW][K + 1];
 #pragma unroll
         for (int st = 0; st < 8; st++) {
@@ -1099,51 +1087,6 @@ __global__ void __launch_bounds__((MbPair2Cfg<N, G>::THREADS), 2) large_mb_pair2
                 }
             }
         }
-#else
-#pragma unroll
-        for (int lvl = L; lvl >= 1; lvl--) {
-            cx ff[CPW][K + 1];
-#pragma unroll
-            for (int c = 0; c < CPW; c++)
-#pragma unroll
-                for (int r = 0; r <= K; r++) {
-                    const double2 t = *hslot(c, (lvl - 1) * (K + 1) + r, ws);
-                    ff[c][r] = cx{t.x, t.y};
-                }
-#pragma unroll
-            for (int col = 0; col <= K; col++) {
-                __builtin_amdgcn_sched_barrier(0);  // one (level, column) operand batch in flight
-                double2 g[K + 1][NSEL];
-#pragma unroll
-                for (int r = 0; r <= K; r++)
-#pragma unroll
-                    for (int sel = 0; sel < NSEL; sel++)
-                        g[r][sel] = (MB2_TSKIP & 1) ? make_double2(1.0 + sel, 0.5 * r) : buffer_ld_d2(grs, gvo,
-                                                 (uint32_t)(16u * sel * ggsw_len) + (uint32_t)((lvl - 1) * (K + 1) + r) * rowb +
-                                                     16u * (uint32_t)(col * M) + 1024u * (uint32_t)s);
-#pragma unroll
-                for (int c = 0; c < CPW; c++) {
-#pragma unroll
-                    for (int r = 0; r <= K; r++) {
-                        double2 kb = g[r][0];
-#pragma unroll
-                        for (int sel = 1; sel < ((MB2_TSKIP & 8) ? 1 : NSEL); sel++) {
-                            kb.x = fma(g[r][sel].x, mono[c][sel].re, fma(-g[r][sel].y, mono[c][sel].im, kb.x));
-                            kb.y = fma(g[r][sel].x, mono[c][sel].im, fma(g[r][sel].y, mono[c][sel].re, kb.y));
-                        }
-                        cx &oc = o[h][c][col];
-                        if (lvl == L && r == 0) {
-                            oc.re = fma(kb.x, ff[c][r].re, -(kb.y * ff[c][r].im));
-                            oc.im = fma(kb.x, ff[c][r].im, kb.y * ff[c][r].re);
-                        } else {
-                            oc.re = fma(kb.x, ff[c][r].re, fma(-kb.y, ff[c][r].im, oc.re));
-                            oc.im = fma(kb.x, ff[c][r].im, fma(kb.y, ff[c][r].re, oc.im));
-                        }
-                    }
-                }
-            }
-        }
-#endif
         __syncthreads();  // every wave has read round h's half buffer
     }
     // ---- phase 3: outputs -> the half buffer as [c][col][16 slots][64], inverse sub-FFTs ----
@@ -1196,12 +1139,12 @@ static bool mb_pair2_enabled() {
 // ---------------------------------------------------------------------------------------
 // Grouped CMUX (k = 1, L = 2).  The top DIF radix-16 is R4 over stride 4, twiddles
 // omega_16^{A c}, R4 (dft16_fwd): its outputs c = G, G+4, G+8, G+12 come from ONE second-layer
-// R4, which needs only output G of each first-layer R4.  So a workgroup per (ciphertext, group G,
-// part) builds KW of the group's sub-blocks straight from the CMUX's packed digits (twist + its
-// share of every radix-16 butterfly), and no f64 spectra cross a launch boundary.  Per CMUX:
+// R4, which needs only output G of each first-layer R4.  So a workgroup per (ciphertext, group G)
+// builds the group's four sub-blocks straight from the CMUX's packed digits (twist + its share of
+// every radix-16 butterfly), and no f64 spectra cross a launch boundary.  Per CMUX:
 //   large_digits_kernel     rotation + both decomposition levels -> packed int16 digits, both rows
 //                           of a position in one 16-byte word
-//   large_group_cmux_kernel per (ct, G, part), 2 KW waves = level li x sub-block s = G + 4 k:
+//   large_group_cmux_kernel per (ct, G), 8 waves = level li x sub-block s = G + 4 k:
 //     1. per half h of the butterflies a: digits -> twist -> the group's radix-16 share for both
 //        rows and levels -> top twiddle W[a c] -> LDS [w][row][a - 512 h]; wave w picks up slots
 //        8h..8h+7 of both rows (WaveFft<1024> natural layout);
@@ -1211,17 +1154,12 @@ static bool mb_pair2_enabled() {
 //        through the pair's own exchange blocks, ordered by pair flags (no workgroup barrier);
 //     4. wave (li, k): inverse sub-FFT of column 1 - li -> U[col][1024 s + position].
 //   large_top_inv_kernel    top DIT radix-16, backward conversion, accumulator update.
-// The operations are the oracle's, in its order, so the outputs stay bit-exact.  LDS: 2 KW blocks
-// of 16 KiB (phase-1 staging, per-wave FFT exchange, MAC exchange) + the sub-FFT twiddle table.
-// KW = 4: 512 threads, 143 KiB, one workgroup per CU; KW = 2: 256 threads, 79 KiB, two per CU
-// (the digits are read by twice as many workgroups; measured slower: 1016 vs 1116 KS+PBS/s).
+// The operations are the oracle's, in its order, so the outputs stay bit-exact.  LDS: 8 blocks
+// of 16 KiB (phase-1 staging, per-wave FFT exchange, MAC exchange) + the sub-FFT twiddle table:
+// 512 threads, 143 KiB, one workgroup per CU (two workgroups of 256 threads and 79 KiB per group,
+// each building half of it, read the digits twice as often and measured slower: 1016 vs 1116
+// KS+PBS/s).
 // ---------------------------------------------------------------------------------------
-#ifndef LARGE_GROUP_SUB
-#define LARGE_GROUP_SUB 1
-#endif
-#ifndef LARGE_GROUP_KW
-#define LARGE_GROUP_KW 4  // sub-blocks per level per group workgroup (4: all of group G; 2: half)
-#endif
 
 // output G of r4_fwd(x0, x1, x2, x3), same expressions
 template <int G>
@@ -1235,40 +1173,25 @@ __device__ __forceinline__ cx r4_out(cx x0, cx x1, cx x2, cx x3) {
     }
 }
 
-// Wave of (level li, sub-block k) in a group workgroup.  1: w = 2k + li -- the two waves of a
-// pair (which sync with each other in the MAC) are adjacent, so they run on different SIMDs and
-// each SIMD holds waves of two different pairs; 0: w = li KW + k (the pair on one SIMD).
 #ifndef LARGE_TSKIP
 #define LARGE_TSKIP 0  // timing-only builds (wrong outputs): 1 no phase 1, 2 no GGSW loads, 4 no U stores
 #endif
 #ifndef LARGE_ACC_AUX
 #define LARGE_ACC_AUX 0  // cache policy of top_inv's accumulator stores (16 = sc1)
 #endif
-#ifndef LARGE_GRP_WMAP
-#define LARGE_GRP_WMAP 1
-#endif
-#ifndef LARGE_GRP_QROT
-#define LARGE_GRP_QROT 1  // group kernel: wave pair -> sub-block rotated per ciphertext (0: pair k on G + 4k)
-#endif
-template <int KW>
-__device__ __forceinline__ constexpr int grp_wave(int li, int k) { return LARGE_GRP_WMAP ? 2 * k + li : li * KW + k; }
+// Wave of (level li, sub-block k) in a group workgroup: w = 2k + li -- the two waves of a pair
+// (which sync with each other in the MAC) are adjacent, so they run on different SIMDs and each
+// SIMD holds waves of two different pairs.
+__device__ __forceinline__ constexpr int grp_wave(int li, int k) { return 2 * k + li; }
 
-template <int KW>
-struct LargeGroupCfg {
-    static_assert(KW == 2 || KW == 4, "2 or 4 sub-blocks per level per workgroup");
+struct GroupCfg {
+    static constexpr int KW = 4;             // sub-blocks per level: all of group G
     static constexpr int WAVES = 2 * KW;
     static constexpr int THREADS = 64 * WAVES;
-    static constexpr int PARTS = 4 / KW;     // workgroups per (ciphertext, group)
     static constexpr int REGION = WAVES * 1024;  // double2 entries: one 16 KiB block per wave
     static constexpr int FLAGS = REGION + SubFft::Lds::s1_len;  // double2 offset of the pair-sync flags
     static constexpr size_t LDS = sizeof(double2) * FLAGS + 8 * KW;  // + one 8-byte flag pair per k
 };
-
-__device__ __forceinline__ uint64_t buffer_ld_u64(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-    typedef unsigned v2u __attribute__((ext_vector_type(2)));
-    const v2u t = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    return ((uint64_t)t.y << 32) | t.x;
-}
 
 // Packed digits of one position pair (j, j + M) of a row: int16 fields (level L at j, level L at
 // j + M, level L-1 at j, level L-1 at j + M); |digit| <= 2^(beta-1) = 2^14.  They live in the
@@ -1279,52 +1202,17 @@ __device__ __forceinline__ uint64_t *group_digits(const LargePbsLaunch &a, int c
     return reinterpret_cast<uint64_t *>(a.spectra + ((size_t)cl * 2 * 2 + 2) * LM);
 }
 
-// Phase 1 step = (row r, column A) of butterfly ap: the inputs b = A + 4m (m = 0..3).  All of a
-// step's loads are issued together and the next step's before this one's arithmetic (a
-// sched_barrier after each load group), so ~20 loads per wave are in flight.
+// Phase 1 step = column A of butterfly ap, both rows: the inputs b = A + 4m (m = 0..3); the twist
+// is loaded once per position, not per row.  All of a step's loads are issued together and the next
+// step's before this one's arithmetic (a sched_barrier after each load group), so ~20 loads per
+// wave are in flight.
 struct GroupDg {
-    uint64_t dg[4];
-    cx tv[4];  // twist at a + 1024 b
+    uint64_t dg[2][4];  // [row][m]
+    cx tv[4];           // twist at a + 1024 b
 };
 template <int A>
 __device__ __forceinline__ void group_load_dg(GroupDg &d, __amdgpu_buffer_rsrc_t dig, __amdgpu_buffer_rsrc_t twist,
-                                              int ap, int r) {
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const int b = A + 4 * m;
-        d.dg[m] = buffer_ld_u64(dig, 16u * ap, 16u * 1024u * b + 8u * r);
-        const double2 t = buffer_ld_d2(twist, 16u * ap, 16u * 1024u * b);
-        d.tv[m] = cx{t.x, t.y};
-    }
-}
-// twist of both levels' digits, first-layer R4 output G of column A, omega_16^{A G}
-template <int A, int G>
-__device__ __forceinline__ void group_compute_dg(const GroupDg &d, cx (&y)[2][4]) {
-    cx z[2][4];  // [li][m]
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const uint64_t w = d.dg[m];
-        const double g0 = (double)(int16_t)(w & 0xffffu), g1 = (double)(int16_t)((w >> 16) & 0xffffu);
-        const double l0 = (double)(int16_t)((w >> 32) & 0xffffu), l1 = (double)(int16_t)(w >> 48);
-        z[0][m] = cmulw(cx{g0, g1}, d.tv[m].re, d.tv[m].im);
-        z[1][m] = cmulw(cx{l0, l1}, d.tv[m].re, d.tv[m].im);
-    }
-#pragma unroll
-    for (int l = 0; l < 2; l++) y[l][A] = tw16_fwd<A * G>(r4_out<G>(z[l][0], z[l][1], z[l][2], z[l][3]));
-}
-
-// phase 1 for butterfly ap of half h: both rows -> LDS staging [w][row][ap - 512 h]
-#ifndef LARGE_GRP_TW_SHARED
-#define LARGE_GRP_TW_SHARED 1  // 1: a phase-1 step is a column A for both rows (twist loaded once per a, not per row)
-#endif
-// both rows of column A: the twist is shared
-struct GroupDg2 {
-    uint64_t dg[2][4];
-    cx tv[4];
-};
-template <int A>
-__device__ __forceinline__ void group_load_dg2(GroupDg2 &d, __amdgpu_buffer_rsrc_t dig, __amdgpu_buffer_rsrc_t twist,
-                                               int ap) {
+                                              int ap) {
 #pragma unroll
     for (int m = 0; m < 4; m++) {
         const int b = A + 4 * m;
@@ -1336,68 +1224,55 @@ __device__ __forceinline__ void group_load_dg2(GroupDg2 &d, __amdgpu_buffer_rsrc
         d.tv[m] = cx{t.x, t.y};
     }
 }
+// one row of a step: twist of both levels' digits, first-layer R4 output G of column A, omega_16^{A G}
 template <int A, int G>
-__device__ __forceinline__ void group_compute_dg2(const GroupDg2 &d, cx (&y)[2][2][4]) {
+__device__ __forceinline__ void group_compute_row(const uint64_t (&dg)[4], const cx (&tv)[4], cx (&y)[2][4]) {
+    cx z[2][4];  // [li][m]
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
-        GroupDg e;
-#pragma unroll
-        for (int m = 0; m < 4; m++) {
-            e.dg[m] = d.dg[r][m];
-            e.tv[m] = d.tv[m];
-        }
-        group_compute_dg<A, G>(e, y[r]);
+    for (int m = 0; m < 4; m++) {
+        const uint64_t w = dg[m];
+        const double g0 = (double)(int16_t)(w & 0xffffu), g1 = (double)(int16_t)((w >> 16) & 0xffffu);
+        const double l0 = (double)(int16_t)((w >> 32) & 0xffffu), l1 = (double)(int16_t)(w >> 48);
+        z[0][m] = cmulw(cx{g0, g1}, tv[m].re, tv[m].im);
+        z[1][m] = cmulw(cx{l0, l1}, tv[m].re, tv[m].im);
     }
+#pragma unroll
+    for (int l = 0; l < 2; l++) y[l][A] = tw16_fwd<A * G>(r4_out<G>(z[l][0], z[l][1], z[l][2], z[l][3]));
+}
+template <int A, int G>
+__device__ __forceinline__ void group_compute_dg(const GroupDg &d, cx (&y)[2][2][4]) {
+#pragma unroll
+    for (int r = 0; r < 2; r++) group_compute_row<A, G>(d.dg[r], d.tv, y[r]);
 }
 
-template <int KW, int G>
-__device__ __forceinline__ void group_phase1(const LargePbsLaunch &a, int cl, int part, int ap, int h, double2 *lds,
-                                             int rot) {
+// phase 1 for butterfly ap of half h: both rows -> LDS staging [w][row][ap - 512 h]
+template <int G>
+__device__ __forceinline__ void group_phase1(const LargePbsLaunch &a, int cl, int ap, int h, double2 *lds, int rot) {
+    constexpr int KW = GroupCfg::KW;
     const __amdgpu_buffer_rsrc_t rdig = make_rsrc(group_digits(a, cl)), rtw = make_rsrc(a.twist);
-#if LARGE_GRP_TW_SHARED
-    cx yy[2][2][4];  // [row][li][A]
+    cx yy[2][2][4];  // [row][li][A]: first-layer outputs, then X[G + 4k]
     {
-        GroupDg2 e0, e1;
-        group_load_dg2<0>(e0, rdig, rtw, ap);
+        GroupDg e0, e1;
+        group_load_dg<0>(e0, rdig, rtw, ap);
         __builtin_amdgcn_sched_barrier(0);
-        group_load_dg2<1>(e1, rdig, rtw, ap);
+        group_load_dg<1>(e1, rdig, rtw, ap);
         __builtin_amdgcn_sched_barrier(0);  // issue the step's loads here, not at their uses
-        group_compute_dg2<0, G>(e0, yy);
-        group_load_dg2<2>(e0, rdig, rtw, ap);
+        group_compute_dg<0, G>(e0, yy);
+        group_load_dg<2>(e0, rdig, rtw, ap);
         __builtin_amdgcn_sched_barrier(0);
-        group_compute_dg2<1, G>(e1, yy);
-        group_load_dg2<3>(e1, rdig, rtw, ap);
+        group_compute_dg<1, G>(e1, yy);
+        group_load_dg<3>(e1, rdig, rtw, ap);
         __builtin_amdgcn_sched_barrier(0);
-        group_compute_dg2<2, G>(e0, yy);
-        group_compute_dg2<3, G>(e1, yy);
+        group_compute_dg<2, G>(e0, yy);
+        group_compute_dg<3, G>(e1, yy);
     }
 #pragma unroll
     for (int r = 0; r < 2; r++) {
         cx (&y)[2][4] = yy[r];
-#else
-    GroupDg e0, e1;
-    group_load_dg<0>(e0, rdig, rtw, ap, 0);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        cx y[2][4];  // [li][A]: first-layer outputs, then X[G + 4k]
-        group_load_dg<1>(e1, rdig, rtw, ap, r);
-        __builtin_amdgcn_sched_barrier(0);  // issue the step's loads here, not at their uses
-        group_compute_dg<0, G>(e0, y);
-        group_load_dg<2>(e0, rdig, rtw, ap, r);
-        __builtin_amdgcn_sched_barrier(0);
-        group_compute_dg<1, G>(e1, y);
-        group_load_dg<3>(e1, rdig, rtw, ap, r);
-        __builtin_amdgcn_sched_barrier(0);
-        group_compute_dg<2, G>(e0, y);
-        if (r == 0) group_load_dg<0>(e0, rdig, rtw, ap, 1);  // next row's first step
-        __builtin_amdgcn_sched_barrier(0);
-        group_compute_dg<3, G>(e1, y);
-#endif
         cx wt[KW];
 #pragma unroll
         for (int k = 0; k < KW; k++) {
-            const int c = G + 4 * (KW * part + k);
+            const int c = G + 4 * k;
             wt[k] = c ? gld(a.wtop + (c - 1) * 1024 + ap) : cx{1.0, 0.0};  // = W[a c]
         }
 #pragma unroll
@@ -1405,11 +1280,10 @@ __device__ __forceinline__ void group_phase1(const LargePbsLaunch &a, int cl, in
             r4_fwd(y[l][0], y[l][1], y[l][2], y[l][3]);  // y[l][k] = X[G + 4k]
 #pragma unroll
             for (int k = 0; k < KW; k++) {
-                const int kg = KW * part + k;  // uniform: part is per workgroup
-                const cx x = KW == 4 ? y[l][k] : (part ? y[l][2 + k] : y[l][k]);
-                const cx v = (G + 4 * kg) ? cmulw(x, wt[k].re, wt[k].im) : x;
-                // sub-block k goes to wave pair (k - rot) mod KW (LARGE_GRP_QROT)
-                lds[(grp_wave<KW>(l, (k - rot) & (KW - 1)) * 2 + r) * 512 + (ap - 512 * h)] = make_double2(v.re, v.im);
+                const cx x = y[l][k];
+                const cx v = (G + 4 * k) ? cmulw(x, wt[k].re, wt[k].im) : x;
+                // sub-block k goes to wave pair (k - rot) mod KW
+                lds[(grp_wave(l, (k - rot) & (KW - 1)) * 2 + r) * 512 + (ap - 512 * h)] = make_double2(v.re, v.im);
             }
         }
     }
@@ -1419,12 +1293,12 @@ __device__ __forceinline__ void group_phase1(const LargePbsLaunch &a, int cl, in
 // LDS flags (GroupSync<2>): wave (LI, k) writes the half of its spectra that the partner needs into
 // its own block, the pair syncs, each reads the other's block; then the same for the column
 // halves.  The four pairs of a workgroup drift independently (no workgroup barrier).
-template <int KW, int LI>
+template <int LI>
 __device__ __forceinline__ void group_mac_pair(cx (&f)[2][16], cx (&v)[16], double2 *lds, int lane, int k,
                                                const double2 *Gb, GroupSync<2> &ps) {
     constexpr int K = 1, L = 2;
-    double2 *own = lds + grp_wave<KW>(LI, k) * 1024 + lane;          // this wave's block
-    const double2 *oth = lds + grp_wave<KW>(1 - LI, k) * 1024 + lane;  // the partner's block
+    double2 *own = lds + grp_wave(LI, k) * 1024 + lane;          // this wave's block
+    const double2 *oth = lds + grp_wave(1 - LI, k) * 1024 + lane;  // the partner's block
 #pragma unroll
     for (int r = 0; r < 2; r++)
 #pragma unroll
@@ -1482,14 +1356,15 @@ __device__ __forceinline__ void group_mac_pair(cx (&f)[2][16], cx (&v)[16], doub
     ps();  // the partner has read this block: it is this wave's FFT exchange buffer again
 }
 
-template <int KW, int G>
-__device__ __forceinline__ void group_cmux_body(const LargePbsLaunch &a, int i, int cl, int part, double2 *lds, int rot) {
+template <int G>
+__device__ __forceinline__ void group_cmux_body(const LargePbsLaunch &a, int i, int cl, double2 *lds, int rot) {
     constexpr int K = 1, L = 2;
-    using Cfg = LargeGroupCfg<KW>;
+    using Cfg = GroupCfg;
+    constexpr int KW = Cfg::KW;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = LARGE_GRP_WMAP ? wave & 1 : wave / KW, k = LARGE_GRP_WMAP ? wave >> 1 : wave % KW;
-    const int sblk = G + 4 * (KW * part + ((k + rot) & (KW - 1)));  // wave pair k runs sub-block k + rot
+    const int li = wave & 1, k = wave >> 1;  // grp_wave(li, k) = wave
+    const int sblk = G + 4 * ((k + rot) & (KW - 1));  // wave pair k runs sub-block k + rot
     double2 *s1 = lds + Cfg::REGION;
     // sub-block stage twiddles W_1024[lane c] = W_M[16 lane c]  (oracle dif_rec tstride 16)
     for (int e = tid; e < SubFft::Lds::s1_len; e += Cfg::THREADS) s1[e] = a.W[16 * (e & 63) * ((e >> 6) + 1)];
@@ -1504,7 +1379,7 @@ __device__ __forceinline__ void group_cmux_body(const LargePbsLaunch &a, int i, 
         if (h) __syncthreads();  // every wave has picked up half 0
 #pragma unroll
         for (int q = 0; q < 512 / Cfg::THREADS; q++)
-            if (!(LARGE_TSKIP & 1)) group_phase1<KW, G>(a, cl, part, 512 * h + Cfg::THREADS * q + tid, h, lds, rot);
+            if (!(LARGE_TSKIP & 1)) group_phase1<G>(a, cl, 512 * h + Cfg::THREADS * q + tid, h, lds, rot);
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 2; r++)
@@ -1521,8 +1396,8 @@ __device__ __forceinline__ void group_cmux_body(const LargePbsLaunch &a, int i, 
     // exchange: 64.4 -> 61.4 us per chunk)
     GroupSync<2> ps;
     ps.mine = lds_addr(lds + Cfg::FLAGS) + 8u * k + 4u * li;
-    if (li) group_mac_pair<KW, 1>(f, v, lds, lane, k, Gb, ps);
-    else group_mac_pair<KW, 0>(f, v, lds, lane, k, Gb, ps);
+    if (li) group_mac_pair<1>(f, v, lds, lane, k, Gb, ps);
+    else group_mac_pair<0>(f, v, lds, lane, k, Gb, ps);
     SubFft::inverse(v, xb, tw, lane, wsync);
     const int col = 1 - li;
     double2 *dst = a.spectra + ((size_t)cl * L * (K + 1) + col) * LM + 1024 * sblk + lane;
@@ -1532,26 +1407,13 @@ __device__ __forceinline__ void group_cmux_body(const LargePbsLaunch &a, int i, 
 // rotation + decomposition of CMUX i for the grouped path at positions j and j + M of row r
 __device__ __forceinline__ uint64_t group_digit_word(const LargePbsLaunch &a, int cl, int r, int j, bool full_odd,
                                                      int rem) {
-    constexpr int L = 2;
-    const int beta = a.base_log;
-    const uint32_t dmask = (1u << beta) - 1;
     const uint64_t *acc = a.acc + ((size_t)cl * 2 + r) * LN;
-    uint64_t w = 0, dd[2];
+    uint64_t dd[2];
     ct1_pair(acc, j, rem, full_odd, dd[0], dd[1]);  // ct1 = X^{a~} acc - acc
-    if (LARGE_DIGIT2) {  // Digit2 (pbs_common.h): the same int16 words in 9 VALU per value
-        uint32_t lv0, lv1;
-        Digit2(beta).pair((uint32_t)(dd[0] >> 32), (uint32_t)(dd[1] >> 32), lv0, lv1);
-        return (uint64_t)lv0 | ((uint64_t)lv1 << 32);
-    }
-#pragma unroll
-    for (int half = 0; half < 2; half++) {
-        const uint64_t d = dd[half];
-        uint32_t st = decomp_state32_hi<L>((uint32_t)(d >> 32), beta);
-        const int32_t dg = decomp_digit32(st, beta, dmask);  // level L
-        const int32_t dl = decomp_digit32(st, beta, dmask);  // level L-1
-        w |= ((uint64_t)((uint32_t)dg & 0xffffu) << (16 * half)) | ((uint64_t)((uint32_t)dl & 0xffffu) << (32 + 16 * half));
-    }
-    return w;
+    // Digit2 (pbs_common.h): the int16 words of two decomp_digit32 per value, in 9 VALU per value
+    uint32_t lv0, lv1;
+    Digit2(a.base_log).pair((uint32_t)(dd[0] >> 32), (uint32_t)(dd[1] >> 32), lv0, lv1);
+    return (uint64_t)lv0 | ((uint64_t)lv1 << 32);
 }
 
 // digits of CMUX i: one thread per (ciphertext, j < M), both rows in one 16-byte store
@@ -1574,25 +1436,22 @@ __global__ void __launch_bounds__(LARGE_DIGT) large_digits_kernel(LargePbsLaunch
     reinterpret_cast<u64x2 *>(group_digits(a, cl))[j] = w;
 }
 
-using GroupCfg = LargeGroupCfg<LARGE_GROUP_KW>;
 __global__ void __launch_bounds__(GroupCfg::THREADS, 2) large_group_cmux_kernel(LargePbsLaunch a, int ct0, int i) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double2 *lds = reinterpret_cast<double2 *>(smem);
-    constexpr int KW = LARGE_GROUP_KW, PARTS = GroupCfg::PARTS;
-    // XCD-aware: the 4 PARTS workgroups of a ciphertext are blocks 8 m + x with the same x (one
-    // XCD), so the digits they all read come from the Infinity Cache once
+    // XCD-aware: the 4 workgroups of a ciphertext are blocks 8 m + x with the same x (one XCD), so
+    // the digits they all read come from the Infinity Cache once
     const int x = blockIdx.x & 7, m = blockIdx.x >> 3;
-    const int cl = x + 8 * (m / (4 * PARTS));
+    const int cl = x + 8 * (m / 4);
     if (cl >= a.chunk_count) return;  // whole workgroup
-    const int part = (m >> 2) % PARTS;
     (void)ct0;
-    // wave pair -> sub-block rotated per ciphertext (LARGE_GRP_QROT, as ONCHIP_QROT)
-    const int rot = (LARGE_GRP_QROT && KW == 4) ? (m >> 2) & 3 : 0;
+    // wave pair -> sub-block rotated per ciphertext (as in the on-chip kernel)
+    const int rot = (m >> 2) & 3;
     switch (m & 3) {
-        case 0: group_cmux_body<KW, 0>(a, i, cl, part, lds, rot); break;
-        case 1: group_cmux_body<KW, 1>(a, i, cl, part, lds, rot); break;
-        case 2: group_cmux_body<KW, 2>(a, i, cl, part, lds, rot); break;
-        default: group_cmux_body<KW, 3>(a, i, cl, part, lds, rot); break;
+        case 0: group_cmux_body<0>(a, i, cl, lds, rot); break;
+        case 1: group_cmux_body<1>(a, i, cl, lds, rot); break;
+        case 2: group_cmux_body<2>(a, i, cl, lds, rot); break;
+        default: group_cmux_body<3>(a, i, cl, lds, rot); break;
     }
 }
 
@@ -1811,7 +1670,7 @@ __global__ void __launch_bounds__(1024) split_inv_digits_kernel(LargePbsLaunch a
         const bool neg0 = (jj0 < 0) != full_odd, neg1 = (jj0 + M < 0) != full_odd;
         const uint64_t d0 = (neg0 ? 0 - x0 : x0) - lo[b];
         const uint64_t d1 = (neg1 ? 0 - x1 : x1) - hi[b];
-        if (LARGE_DIGIT2 && a.base_log * 2 <= 30) {  // Digit2: the same words, 32-bit
+        if (a.base_log * 2 <= 30) {  // Digit2: the same words, 32-bit
             uint32_t lv0, lv1;
             Digit2(a.base_log).pair((uint32_t)(d0 >> 32), (uint32_t)(d1 >> 32), lv0, lv1);
             dig[2 * j + row] = (uint64_t)lv0 | ((uint64_t)lv1 << 32);
@@ -1856,9 +1715,6 @@ __global__ void __launch_bounds__(1024) split_inv_digits_kernel(LargePbsLaunch a
 #ifndef ONCHIP_MAC_SB
 #define ONCHIP_MAC_SB 4  // MAC slots per scheduling region (GGSW loads in flight)
 #endif
-#ifndef ONCHIP_QROT
-#define ONCHIP_QROT 1  // wave pair -> sub-block rotated per workgroup (0: pair p on sub-block p)
-#endif
 // L = 2: WaveFft exchange bases recomputed per transform (bit 1 la, bit 2 qa).  Hoisted out of the
 // CMUX loop, their 32 XOR images were spilled to scratch inside it (<8192, true, 2>: 132 B private,
 // 15 scratch stores + 33 loads per CMUX, vmcnt(0) waits on the GGSW prefetch; <4096, true, 2>: 84 B).
@@ -1871,38 +1727,28 @@ __global__ void __launch_bounds__(1024) split_inv_digits_kernel(LargePbsLaunch a
 #ifndef ONCHIP_LAUNDER_4096
 #define ONCHIP_LAUNDER_4096 1
 #endif
-#ifndef ONCHIP_4096_CPW
-#define ONCHIP_4096_CPW 1  // N = 4096: 1 = one ciphertext per 256-thread workgroup (two workgroups per CU,
-                           // independent barriers); 2 = two ciphertexts per 512-thread workgroup
-#endif
+// One ciphertext per workgroup: at N = 4096 that is 256 threads, two workgroups per CU with
+// independent barriers (two ciphertexts in one 512-thread workgroup were the alternative).
 template <int N>
 struct OnchipCfg {
     static constexpr int M = N / 2, R = M / 1024;
-    static constexpr int CPW = R == 4 ? 1 : ONCHIP_4096_CPW;  // ciphertexts per workgroup
-    static constexpr int THREADS = 256 * R / 2 * CPW;         // 2 R waves per ciphertext
+    static constexpr int THREADS = 128 * R;                   // 2 R waves
     static constexpr int WAVES = THREADS / 64;
     static constexpr int WPS = THREADS / 256;                 // waves per SIMD of one workgroup
     static constexpr int MIN_WPS = 2;                         // 2 waves per SIMD per CU: 256 VGPRs
-    static constexpr int TPC = THREADS / CPW;  // threads per ciphertext
-    static constexpr int H = 1024 / TPC;       // top-stage butterflies per thread
+    static constexpr int H = 1024 / THREADS;  // top-stage butterflies per thread
     static constexpr int BUF = SubFft::XL;    // double2 per wave buffer
     static constexpr int S1 = WAVES * BUF;    // twiddle table offset (double2 units)
     static constexpr int FLAGS = S1 + SubFft::Lds::s1_len;  // pair-sync flags (double2 offset), one word per wave
     static constexpr size_t LDS = sizeof(double2) * FLAGS + 4 * WAVES;
-    static_assert(R == 4 || R == 2, "CPW ciphertexts x R sub-blocks x 2 rows of waves");
-    static_assert(WAVES * BUF * sizeof(double2) == CPW * 2 * M * sizeof(acc_pair), "the rotation's pairs fill the wave buffers");
+    static_assert(R == 4 || R == 2, "R sub-blocks x 2 rows of waves");
+    static_assert(WAVES * BUF * sizeof(double2) == 2 * M * sizeof(acc_pair), "the rotation's pairs fill the wave buffers");
     static_assert(LDS <= 160 * 1024 / (MIN_WPS / WPS), "LDS of the workgroups one CU holds");
 };
 
 // MAC of level L - LI for one sub-block: both rows' spectra from their buffers F (row r at
 // F + r BUF; the own one too, so its registers are free here); o accumulates over levels L..1
 // and rows 0..k in the oracle's order (sub_cmux_body's forms)
-#ifndef ONCHIP_PAIRSYNC
-#define ONCHIP_PAIRSYNC 1  // the publish -> MAC sync through the pair's LDS flags instead of a barrier
-#endif
-#ifndef ONCHIP_TPF
-#define ONCHIP_TPF 1  // top-stage twist / twiddle loads issued before the barrier preceding their use
-#endif
 #ifndef ONCHIP_PF
 #define ONCHIP_PF 4  // MAC slots whose GGSW operands are issued before the publish barrier (0: none)
 #endif
@@ -1963,46 +1809,29 @@ __device__ __forceinline__ void onchip_mac(__amdgpu_buffer_rsrc_t rg, uint32_t g
     }
 }
 
-// decompose64<2> in 32-bit registers when base_log * 2 <= 30 (pbs_common.h decomp_state32: the
-// same digits)
-template <bool D32>
-__device__ __forceinline__ void onchip_decompose(uint64_t x, int beta, int32_t (&d)[2]) {
-    if constexpr (D32) {
-        uint32_t st = decomp_state32<2>(x, beta);
-        const uint32_t mask = (1u << beta) - 1;
-        d[0] = decomp_digit32(st, beta, mask);
-        d[1] = decomp_digit32(st, beta, mask);
-    } else {
-        decompose64<2>(x, beta, d);
-    }
-}
-
-#ifndef ONCHIP_DIGIT2
-#define ONCHIP_DIGIT2 1  // 0: two decomp_digit32 per value (A/B of Digit2, pbs_common.h)
-#endif
 // both levels of the values at j and j + M as the int16 quad the top DIF reads: level L at j, j + M
-// in the low dword, level L-1 in the high dword
+// in the low dword, level L-1 in the high dword.  D32 (base_log * 2 <= 30): Digit2 (pbs_common.h),
+// the same digits as decompose64<2>
 template <bool D32>
 __device__ __forceinline__ uint64_t onchip_pack2(uint64_t v0, uint64_t v1, int beta, const Digit2 &dg2) {
-    if constexpr (D32 && ONCHIP_DIGIT2) {
+    if constexpr (D32) {
         uint32_t lv0, lv1;
         dg2.pair((uint32_t)(v0 >> 32), (uint32_t)(v1 >> 32), lv0, lv1);
         return (uint64_t)lv0 | ((uint64_t)lv1 << 32);
     } else {
         int32_t e0[2], e1[2];
-        onchip_decompose<D32>(v0, beta, e0);
-        onchip_decompose<D32>(v1, beta, e1);
+        decompose64<2>(v0, beta, e0);
+        decompose64<2>(v1, beta, e1);
         return ((uint64_t)((uint32_t)e0[0] & 0xffffu)) | ((uint64_t)((uint32_t)e1[0] & 0xffffu) << 16) |
                ((uint64_t)((uint32_t)e0[1] & 0xffffu) << 32) | ((uint64_t)((uint32_t)e1[1] & 0xffffu) << 48);
     }
 }
 
-// L = 1: the one signed digit (decompose64<1>; 32-bit when base_log <= 30)
+// L = 1: the one signed digit (decompose64<1>; D32, base_log <= 30: the classic kernel's 3-op DigitL1)
 template <bool D32>
-__device__ __forceinline__ int32_t onchip_decompose1(uint64_t x, int beta) {
+__device__ __forceinline__ int32_t onchip_digit1(uint64_t x, int beta, const DigitL1 &dl1) {
     if constexpr (D32) {
-        uint32_t st = decomp_state32<1>(x, beta);
-        return decomp_digit32(st, beta, (1u << beta) - 1);
+        return dl1((uint32_t)(x >> 32));
     } else {
         int32_t d[1];
         decompose64<1>(x, beta, d);
@@ -2025,23 +1854,19 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
     using S = Split<N>;
     using Cfg = OnchipCfg<N>;
     static_assert(L == 1 || L == 2, "one or two decomposition levels");
-    constexpr int K = 1, M = S::M, R = S::R, H = Cfg::H, BUF = Cfg::BUF, CPW = Cfg::CPW, TPC = Cfg::TPC;
+    constexpr int K = 1, M = S::M, R = S::R, H = Cfg::H, BUF = Cfg::BUF, TPC = Cfg::THREADS;
     constexpr size_t ggsw_len = (size_t)L * (K + 1) * (K + 1) * M;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double2 *lds = reinterpret_cast<double2 *>(smem);
     acc_pair *pairs = reinterpret_cast<acc_pair *>(smem);  // rotation view: [row][M] pairs
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    // wave = 2 R c + 2 q + wr: ciphertext c of the workgroup, sub-block q, row (forward) = column
-    // (MAC, inverse) wr; thread t works for ciphertext ctl = t / TPC as thread tc = t mod TPC
-    // sub-block of the wave pair, rotated by the workgroup's index among those of its XCD
-    // (ONCHIP_QROT) so that the CUs of an XCD do not all stream the same GGSW slice at once
-    const int q = ((wave >> 1) + (ONCHIP_QROT ? (int)(blockIdx.x >> 3) : 0)) & (R - 1), wr = wave & 1;
-    const int ctl = CPW == 1 ? 0 : t / TPC, tc = CPW == 1 ? t : t % TPC;
-    const int cb = 2 * R * ctl;  // this thread's ciphertext's first wave buffer
-    const int wbuf = cb + 2 * q + wr;  // this wave's buffer: sub-block q, row / column wr
-    const int ct_raw = CPW == 1 ? (int)blockIdx.x : (int)blockIdx.x * CPW + ctl;
-    const int ct = CPW == 1 ? ct_raw : min(ct_raw, a.count - 1);  // a padding slot repeats the last ciphertext
+    // wave = 2 q' + wr: row (forward) = column (MAC, inverse) wr of sub-block q = q' rotated by the
+    // workgroup's index among those of its XCD, so that the CUs of an XCD do not all stream the same
+    // GGSW slice at once
+    const int q = ((wave >> 1) + (int)(blockIdx.x >> 3)) & (R - 1), wr = wave & 1;
+    const int wbuf = 2 * q + wr;  // this wave's buffer: sub-block q, row / column wr
+    const int ct = (int)blockIdx.x;
     double2 *s1 = lds + Cfg::S1;
     // sub-block stage twiddles W_1024[lane c] = W_M[R lane c]  (oracle dif_rec tstride R)
     for (int e = t; e < SubFft::Lds::s1_len; e += Cfg::THREADS) s1[e] = a.W[R * (e & 63) * ((e >> 6) + 1)];
@@ -2055,7 +1880,7 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
     const uint64_t *in = a.lwe_in + (size_t)ct * (a.n + 1);
     // twist and top-stage twiddles through buffer loads: one VGPR offset, the rest in SGPRs
     const __amdgpu_buffer_rsrc_t rtw = make_rsrc(a.twist), rwt = make_rsrc(a.wtop);
-    const uint32_t tvo = 16u * tc;
+    const uint32_t tvo = 16u * t;
     auto ld_cx = [](__amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) {
         const double2 x = buffer_ld_d2(r, vo, so);
         return cx{x.x, x.y};
@@ -2080,7 +1905,7 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
             for (int h = 0; h < H; h++)
 #pragma unroll
                 for (int b = 0; b < R; b++) {
-                    const int j = tc + TPC * h + 1024 * b;
+                    const int j = t + TPC * h + 1024 * b;
                     lo[r][h][b] = init(r, j);
                     hi[r][h][b] = init(r, j + M);
                 }
@@ -2092,13 +1917,13 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
     // accumulator pair (row r, j) <-> LDS slot (2 (j >> 10) + r) BUF + (j & 1023): the slots thread t
     // owns, (2 b + r) BUF + t + 512 h, are exactly the top-stage / top-inverse slots of its butterflies,
     // so the top inverse writes the updated pairs in place (no barrier between its reads and them)
-    auto pslot = [&](int r, int j) { return (cb + 2 * (j >> 10) + r) * BUF + (j & 1023); };
+    auto pslot = [&](int r, int j) { return (2 * (j >> 10) + r) * BUF + (j & 1023); };
 #pragma unroll
     for (int r = 0; r < 2; r++)
 #pragma unroll
         for (int h = 0; h < H; h++)
 #pragma unroll
-            for (int b = 0; b < R; b++) pairs[(cb + 2 * b + r) * BUF + tc + TPC * h] = acc_pair{lo[r][h][b], hi[r][h][b]};
+            for (int b = 0; b < R; b++) pairs[(2 * b + r) * BUF + t + TPC * h] = acc_pair{lo[r][h][b], hi[r][h][b]};
 
     uint64_t a_next = in[0];
     for (int i = 0; i < a.n; i++) {
@@ -2115,7 +1940,7 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
             for (int h = 0; h < H; h++)
 #pragma unroll
                 for (int b = 0; b < R; b++) {
-                    const int j = tc + TPC * h + 1024 * b;
+                    const int j = t + TPC * h + 1024 * b;
                     const int jj0 = j - rem;  // in (-N, M)
                     const acc_pair rot = (ONCHIP_TSKIP & 16) ? acc_pair{lo[r][h][b] * 3, hi[r][h][b]} : pairs[pslot(r, jj0 & (M - 1))];
                     const bool swap = jj0 < 0 && jj0 >= -M;
@@ -2126,14 +1951,7 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
                                                         beta, dg2);
                     } else {  // one level: |digit| <= 2^(beta - 1) (2^21 at base 2^22) -- two int32 fields
                         const uint64_t v0 = (neg0 ? 0 - x0 : x0) - lo[r][h][b], v1 = (neg1 ? 0 - x1 : x1) - hi[r][h][b];
-                        int32_t e0, e1;
-                        if constexpr (D32 && ONCHIP_DIGIT2) {  // the classic kernel's 3-op digit (DigitL1)
-                            e0 = dl1((uint32_t)(v0 >> 32));
-                            e1 = dl1((uint32_t)(v1 >> 32));
-                        } else {
-                            e0 = onchip_decompose1<D32>(v0, beta);
-                            e1 = onchip_decompose1<D32>(v1, beta);
-                        }
+                        const int32_t e0 = onchip_digit1<D32>(v0, beta, dl1), e1 = onchip_digit1<D32>(v1, beta, dl1);
                         pk[r][h][b] = (uint64_t)(uint32_t)e0 | ((uint64_t)(uint32_t)e1 << 32);
                     }
                 }
@@ -2151,7 +1969,7 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
 #pragma unroll
             for (int h = 0; h < H; h++) top_loads_h(h);
         };
-        if (ONCHIP_TPF) top_loads();
+        top_loads();
         __syncthreads();  // the pairs are read: the region becomes the wave buffers
         const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.fbsk + (size_t)i * ggsw_len + (size_t)wr * M + 1024 * q);
         cx o[16];
@@ -2161,8 +1979,8 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
             // (level L-1: per butterfly half, where they are used -- the MAC outputs are live)
 #pragma unroll
             for (int h = 0; h < H; h++) {
-                const int a0 = tc + TPC * h;
-                if (!ONCHIP_TPF || LI == 1) top_loads_h(h);
+                const int a0 = t + TPC * h;
+                if (LI == 1) top_loads_h(h);
 #pragma unroll
                 for (int r = 0; r < 2; r++) {
                     cx u[R];
@@ -2180,11 +1998,11 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
                         u[b] = cmulw(cx{(double)d0, (double)d1}, tv[h][b].re, tv[h][b].im);
                     }
                     if (!(ONCHIP_TSKIP & 8)) dftR_fwd<R>(u);
-                    lds[(cb + r) * BUF + a0] = make_double2(u[0].re, u[0].im);
+                    lds[r * BUF + a0] = make_double2(u[0].re, u[0].im);
 #pragma unroll
                     for (int c = 1; c < R; c++) {
                         const cx y = cmulw(u[c], wq[h][c].re, wq[h][c].im);
-                        lds[(cb + 2 * c + r) * BUF + a0] = make_double2(y.re, y.im);
+                        lds[(2 * c + r) * BUF + a0] = make_double2(y.re, y.im);
                     }
                 }
             }
@@ -2204,8 +2022,7 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
             double2 pf[onchip_pfs<M, L>()][2];
 #pragma unroll
             for (int s = 0; s < onchip_pf<M, L>(); s++) onchip_ggsw<M, LI, L>(rg, 16u * lane, s, pf[s][0], pf[s][1]);
-            if (ONCHIP_PAIRSYNC) ps();  // only the partner reads this spectrum
-            else __syncthreads();
+            ps();  // only the partner reads this spectrum: the pair's LDS flags, not a barrier
             // ---- MAC of this level, column wr ----
             onchip_mac<M, BUF, LI, L>(rg, 16u * lane, lds + (wbuf & ~1) * BUF + lane, o, pf);
             __syncthreads();  // the partner has read this wave's spectrum
@@ -2217,30 +2034,29 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
         wsync();
 #pragma unroll
         for (int b = 0; b < 16; b++) own[lane + 64 * b] = make_double2(o[b].re, o[b].im);
-        if (ONCHIP_TPF) top_loads();
+        top_loads();
         __syncthreads();
         // ---- top DIT radix-4, backward conversion, acc += (large_top_inv) ----
-        if (!ONCHIP_TPF) top_loads();
 #pragma unroll
         for (int h = 0; h < H; h++) {
-            const int a0 = tc + TPC * h;
+            const int a0 = t + TPC * h;
 #pragma unroll
             for (int col = 0; col < 2; col++) {
                 cx u[R];
                 {
-                    const double2 x = lds[(cb + col) * BUF + a0];
+                    const double2 x = lds[col * BUF + a0];
                     u[0] = cx{x.x, x.y};
                 }
 #pragma unroll
                 for (int c = 1; c < R; c++) {
-                    const double2 x = lds[(cb + 2 * c + col) * BUF + a0];
+                    const double2 x = lds[(2 * c + col) * BUF + a0];
                     u[c] = cmulw(cx{x.x, x.y}, wq[h][c].re, -wq[h][c].im);
                 }
                 if (!(ONCHIP_TSKIP & 8)) dftR_inv<R>(u);
 #pragma unroll
                 for (int b = 0; b < R; b++) {
                     backward_add(u[b], tv[h][b], lo[col][h][b], hi[col][h][b], k32);
-                    pairs[(cb + 2 * b + col) * BUF + a0] = acc_pair{lo[col][h][b], hi[col][h][b]};  // = slot read above
+                    pairs[(2 * b + col) * BUF + a0] = acc_pair{lo[col][h][b], hi[col][h][b]};  // = slot read above
                 }
             }
         }
@@ -2248,14 +2064,13 @@ __global__ void __launch_bounds__(OnchipCfg<N>::THREADS, OnchipCfg<N>::MIN_WPS /
     // ---- sample extract at degree 0 (large_extract_kernel) from the pairs ----
     __syncthreads();
     uint64_t *out = a.lwe_out + (size_t)ct * ((size_t)K * N + 1);
-    if (CPW > 1 && ct_raw >= a.count) return;  // padding slot: nothing to store (no barrier follows)
-    for (int e = tc; e < N; e += TPC) {
+    for (int e = t; e < N; e += TPC) {
         const int p = e == 0 ? 0 : N - e;
         const acc_pair pr = pairs[pslot(0, p & (M - 1))];
         const uint64_t x = p >= M ? pr.y : pr.x;
         out[e] = e == 0 ? x : 0 - x;
     }
-    if (tc == 0) out[N] = lo[1][0][0];  // row 1 position 0: the body
+    if (t == 0) out[N] = lo[1][0][0];  // row 1 position 0: the body
 }
 
 static bool onchip_enabled() {
@@ -2299,23 +2114,6 @@ static bool onchip_enabled() {
 #ifndef QUAD_STAMPS
 #define QUAD_STAMPS 0  // diagnostic builds: s_memtime at the phase boundaries of CMUX 200 (waves 0 and 4 of
                        // ciphertext 0's workgroup q = 0), written over that ciphertext's output words 1..26
-#endif
-#ifndef QUAD_TPF
-#define QUAD_TPF 1  // the top stages' twist / W loads issued ahead of the barrier before their use
-#endif
-#ifndef QUAD_OWNU
-#define QUAD_OWNU 0  // 1: the workgroup's own U_q read back from LDS, not from the exchange buffer -- the
-                     // per-sub-block branch serialises the U loads: 13.07-13.68 vs 12.63 ms per call
-                     // (profiles/r06_quad_ab.txt)
-#endif
-#ifndef QUAD_PPOLL
-#define QUAD_PPOLL 1  // the R exchange flags polled by R lanes at once (0: lane 0 polls them in turn)
-#endif
-#ifndef QUAD_WPOLL
-#define QUAD_WPOLL 0  // 1: every wave polls the flags itself instead of wave 0 + a workgroup barrier
-#endif
-#ifndef QUAD_PKFENCE
-#define QUAD_PKFENCE 1  // the digits computed before the barrier that ends the rotation
 #endif
 #ifndef QUAD_TSKIP
 #define QUAD_TSKIP 0  // timing-only builds (wrong outputs): 1 no flag wait, 2 no forward sub-FFTs, 4 no inverse
@@ -2423,7 +2221,7 @@ __global__ void __launch_bounds__(512, 1) quad_cmux_kernel(LargePbsLaunch a, int
         const bool full_odd = (at / N) & 1;
         const int rem = at % N;
         const int par = i & 1;
-        // the top stage's twist and W[a0 q], issued ahead of the barrier (QUAD_TPF)
+        // the top stage's twist and W[a0 q], issued ahead of the barrier before their use
         cx tvh[H][R], wqh[H];
         auto top_tables = [&]() {
             const uint32_t z = (uint32_t)opaque_zero();
@@ -2438,7 +2236,7 @@ __global__ void __launch_bounds__(512, 1) quad_cmux_kernel(LargePbsLaunch a, int
                 wqh[h] = cx{y.x, y.y};
             }
         };
-        if (QUAD_TPF) top_tables();
+        top_tables();
         __syncthreads();  // every pair written (and, at i = 0, the twiddle table)
         stamp(i, 1);
         // ---- rotation + decomposition (the on-chip kernel's) ----
@@ -2459,24 +2257,16 @@ __global__ void __launch_bounds__(512, 1) quad_cmux_kernel(LargePbsLaunch a, int
                     if constexpr (L == 2) {
                         pk[r][h][b] = onchip_pack2<D32>(v0, v1, beta, dg2);
                     } else {  // |digit| <= 2^(beta - 1): two int32 fields
-                        int32_t e0, e1;
-                        if constexpr (D32) {
-                            e0 = dl1((uint32_t)(v0 >> 32));
-                            e1 = dl1((uint32_t)(v1 >> 32));
-                        } else {
-                            e0 = onchip_decompose1<D32>(v0, beta);
-                            e1 = onchip_decompose1<D32>(v1, beta);
-                        }
+                        const int32_t e0 = onchip_digit1<D32>(v0, beta, dl1), e1 = onchip_digit1<D32>(v1, beta, dl1);
                         pk[r][h][b] = (uint64_t)(uint32_t)e0 | ((uint64_t)(uint32_t)e1 << 32);
                     }
-                    if (QUAD_PKFENCE) asm volatile("" : "+v"(pk[r][h][b]));  // digits before the barrier: 32
-                                                                            // registers live across it, not 64
+                    asm volatile("" : "+v"(pk[r][h][b]));  // digits before the barrier that ends the rotation:
+                                                           // 32 registers live across it, not 64
                 }
         stamp(i, 2);
         __syncthreads();  // the pairs are read: the region becomes the spectra
         stamp(i, 3);
         // ---- top DIF output q of both rows and levels ----
-        if (!QUAD_TPF) top_tables();
         if constexpr (R == 4) {
             switch (q) {
                 case 0: quad_top<N, 0, H, L>(lds, pk, tvh, wqh, t); break;
@@ -2520,11 +2310,6 @@ __global__ void __launch_bounds__(512, 1) quad_cmux_kernel(LargePbsLaunch a, int
                     v[sl] = cx{y.x, y.y};
                 }
                 if (!(QUAD_TSKIP & 4)) SubFft::inverse(v, reinterpret_cast<cx *>(colb), tw, lane, wsync);
-                if (QUAD_OWNU) {
-                    wsync();  // the inverse's own exchange reads of colb are done
-#pragma unroll
-                    for (int b = 0; b < 16; b++) colb[lane + 64 * b] = make_double2(v[b].re, v[b].im);  // own U_q[c]
-                }
                 double2 *dst = quad_u<N>(a, cnt, cl, par, q, wave);
                 const __amdgpu_buffer_rsrc_t ru = make_rsrc(dst);
                 if (!(QUAD_TSKIP & 32))
@@ -2596,14 +2381,14 @@ __global__ void __launch_bounds__(512, 1) quad_cmux_kernel(LargePbsLaunch a, int
                 }
             }
         };
-        if (QUAD_TPF) dit_tables();
+        dit_tables();
         __syncthreads();  // U_q stored and drained by both storing waves
         stamp(i, 9);
         // ---- exchange: the R workgroups' U of CMUX i ----
-        if (QUAD_PPOLL && (QUAD_WPOLL || wave == 0)) {
-            // lanes 0..R-1 poll the R flags together: one L2 round trip per poll instead of R in turn
-            // (QUAD_WPOLL: every wave polls for itself, so no workgroup barrier follows the wait)
-            if (wave == 0 && lane == 0)
+        if (wave == 0) {
+            // lanes 0..R-1 poll the R flags together: one L2 round trip per poll instead of R in turn;
+            // the other waves wait at the workgroup barrier below
+            if (lane == 0)
                 __hip_atomic_store(flags + q * (Cfg::FLAG_BYTES / 4), (uint32_t)(i + 1), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t *f = flags + (lane < R ? lane : 0) * (Cfg::FLAG_BYTES / 4);
@@ -2613,28 +2398,14 @@ __global__ void __launch_bounds__(512, 1) quad_cmux_kernel(LargePbsLaunch a, int
                 if (__all(v >= (uint32_t)(i + 1))) break;
                 __builtin_amdgcn_s_sleep(1);
             }
+            // a partner that never arrived (the device's CUs held by another process's quad grid):
+            // the outputs are invalid -- recorded for the host (tfhe_mi355 fails the call), no hang
             if (spin == QUAD_SPIN_MAX && lane == 0 && a.quad_fail)
                 __hip_atomic_store(a.quad_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else if (!QUAD_PPOLL && t == 0) {
-            __hip_atomic_store(flags + q * (Cfg::FLAG_BYTES / 4), (uint32_t)(i + 1), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            for (int p = 0; p < ((QUAD_TSKIP & 1) ? 0 : R); p++) {
-                const uint32_t *f = flags + p * (Cfg::FLAG_BYTES / 4);
-                uint32_t spin = 0;
-                for (; spin < QUAD_SPIN_MAX; spin++) {
-                    if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (uint32_t)(i + 1)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                // a partner that never arrived (the device's CUs held by another process's quad grid):
-                // the outputs are invalid -- recorded for the host (tfhe_mi355 fails the call), no hang
-                if (spin == QUAD_SPIN_MAX && a.quad_fail)
-                    __hip_atomic_store(a.quad_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
         }
-        if (!(QUAD_PPOLL && QUAD_WPOLL)) __syncthreads();
+        __syncthreads();
         stamp(i, 10);
         // ---- top DIT radix-4 of both columns, backward_add (large_top_inv), full width ----
-        if (!QUAD_TPF) dit_tables();
 #pragma unroll
         for (int h = 0; h < H; h++) {
             const int a0 = t + TPC * h;
@@ -2646,10 +2417,9 @@ __global__ void __launch_bounds__(512, 1) quad_cmux_kernel(LargePbsLaunch a, int
                 for (int c = 0; c < R; c++) {
                     typedef unsigned v4u __attribute__((ext_vector_type(4)));
                     cx y;
-                    if (QUAD_OWNU && c == q) {  // this workgroup's own sub-block: kept in LDS by the inverse wave
-                        const double2 z = lds[(4 + col) * BUF + a0];
-                        y = cx{z.x, z.y};
-                    } else if (QUAD_TSKIP & 16) {
+                    // (the own U_q too: reading it back from LDS instead put a per-sub-block branch among
+                    // the U loads, 13.07-13.68 vs 12.63 ms per call, profiles/r06_quad_ab.txt)
+                    if (QUAD_TSKIP & 16) {
                         const double2 z = lds[(c * 2 + col) * BUF + a0];
                         y = cx{z.x, z.y};
                     } else {
@@ -2819,138 +2589,6 @@ size_t large_pbs_scratch_per_ct(int N, int k, int L) {
     return std::max(split, quad);
 }
 
-// TFHE_MI355_LARGE_SPLIT=1: the N = 32768, L = 2 CMUX through the split path (top_fwd / sub /
-// top_inv) instead of the grouped one -- same Fourier key layout, same outputs (A/B switch)
-static bool large_grouped_enabled() {
-    static const bool v = [] {
-        const char *e = std::getenv("TFHE_MI355_LARGE_SPLIT");
-        return !(e && e[0] && e[0] != '0');
-    }();
-    return v;
-}
-
-// TFHE_MI355_DSUB=0: the classic L = 2 split CMUX at N <= 8192 through large_top_fwd +
-// large_sub_kernel instead of the digits-fed path (A/B switch)
-static bool large_dsub_enabled() {
-    static const bool v = [] {
-        const char *e = std::getenv("TFHE_MI355_DSUB");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// TFHE_MI355_SPLIT_FUSED=0: the digits-fed CMUX with separate large_top_inv and split_digits
-// launches instead of split_inv_digits_kernel (A/B switch)
-static bool split_fused_enabled() {
-    static const bool v = [] {
-        const char *e = std::getenv("TFHE_MI355_SPLIT_FUSED");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// TFHE_MI355_PAIR_SUB=1: the classic split CMUX (L <= 2) through large_pair_sub_kernel too (A/B)
-static bool large_pair_sub_classic() {
-    static const bool v = [] {
-        const char *e = std::getenv("TFHE_MI355_PAIR_SUB");
-        return e && e[0] && e[0] != '0';
-    }();
-    return v;
-}
-
-// The grouped N = 32768 CMUX on two CU-masked lanes (round 6).  Per chunk-CMUX the group kernel
-// is FP64-bound (VALU busy 0.42) and the two streaming kernels (large_top_inv, large_digits: 43 % of
-// the time) run at the Infinity-Cache streaming ceiling, one after the other on every CU.  Here two
-// chunks A and B alternate: lane_c (most CUs) runs group(A, i) while lane_m (the other CUs) runs
-// top_inv(B, i - 1) + digits(B, i), then the roles swap; cross-lane order by events.  Per lane the
-// kernel sequence and its arguments are those of the one-stream path, so outputs are identical.
-//   lane_m: init(A) digits(A,0) [dA]  init(B) digits(B,0) [dB]
-//   per CMUX i:  lane_c: <dA> group(A,i) [gA]  <dB> group(B,i) [gB]
-//                lane_m: <gA> top_inv(A,i) digits(A,i+1) [dA]  <gB> top_inv(B,i) digits(B,i+1) [dB]
-//   lane_m: extract(A) extract(B); the launch stream waits for both lanes
-static hipError_t launch_grouped_lanes(const LargePbsLaunch &a0, hipStream_t s, size_t per_ct) {
-    constexpr int N = LN, K = 1;
-    const int lchunk = (int)std::min<size_t>((size_t)a0.count, a0.scratch_bytes / per_ct / 2);
-    if (lchunk <= 0) return hipErrorInvalidValue;
-    hipStream_t C = a0.lane_c, Mst = a0.lane_m;
-    hipEvent_t ev[5] = {};
-    hipError_t e = hipSuccess;
-    for (auto &x : ev)
-        if ((e = hipEventCreateWithFlags(&x, hipEventDisableTiming)) != hipSuccess) return e;
-    hipEvent_t &start = ev[0], &dA = ev[1], &dB = ev[2], &gA = ev[3], &gB = ev[4];
-    (void)hipEventRecord(start, s);  // the caller's prior work (inputs, LUTs) before either lane
-    (void)hipStreamWaitEvent(C, start, 0);
-    (void)hipStreamWaitEvent(Mst, start, 0);
-    LargePbsLaunch la[2] = {a0, a0};
-    for (int l = 0; l < 2; l++) {
-        la[l].levels = 2;
-        la[l].acc = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(a0.scratch) + (size_t)l * lchunk * per_ct);
-        la[l].spectra = reinterpret_cast<double2 *>(reinterpret_cast<char *>(la[l].acc) +
-                                                    (size_t)lchunk * (K + 1) * N * sizeof(uint64_t));
-    }
-    hipEvent_t *dev[2] = {&dA, &dB}, *gev[2] = {&gA, &gB};
-    for (int ct0 = 0; ct0 < a0.count; ct0 += 2 * lchunk) {
-        int c0[2], cnt[2];
-        for (int l = 0; l < 2; l++) {
-            c0[l] = ct0 + l * lchunk;
-            cnt[l] = std::max(0, std::min(lchunk, a0.count - c0[l]));
-            la[l].chunk_count = cnt[l];
-        }
-        const int lanes = cnt[1] > 0 ? 2 : 1;
-        auto grp_blocks = [&](int l) { return (unsigned)((cnt[l] + 7) / 8) * 8 * 4 * GroupCfg::PARTS; };
-        auto dig_blocks = [&](int l) { return (unsigned)((cnt[l] + 7) / 8) * 8 * (LM / LARGE_DIGT); };
-        auto top_blocks = [&](int l) { return (unsigned)cnt[l] * (K + 1) * (1024 / TOPT); };
-        for (int l = 0; l < lanes; l++) {
-            const size_t init_elems = (size_t)cnt[l] * (K + 1) * N;
-            hipLaunchKernelGGL((large_init_kernel<N, K>), dim3((unsigned)((init_elems + 255) / 256)), dim3(256), 0, Mst,
-                               la[l], c0[l], cnt[l]);
-            {
-                TimedLaunch tl(a0.timer, "large_digits_kernel", Mst);
-                hipLaunchKernelGGL(large_digits_kernel, dim3(dig_blocks(l)), dim3(LARGE_DIGT), 0, Mst, la[l], c0[l], 0);
-            }
-            (void)hipEventRecord(*dev[l], Mst);
-        }
-        for (int i = 0; i < a0.n; i++) {
-            for (int l = 0; l < lanes; l++) {
-                (void)hipStreamWaitEvent(C, *dev[l], 0);
-                {
-                    TimedLaunch tl(a0.timer, "large_group_cmux_kernel", C);
-                    hipLaunchKernelGGL(large_group_cmux_kernel, dim3(grp_blocks(l)), dim3(GroupCfg::THREADS), GroupCfg::LDS, C,
-                                       la[l], c0[l], i);
-                }
-                (void)hipEventRecord(*gev[l], C);
-            }
-            for (int l = 0; l < lanes; l++) {
-                (void)hipStreamWaitEvent(Mst, *gev[l], 0);
-                {
-                    TimedLaunch tl(a0.timer, "large_top_inv_kernel", Mst);
-                    hipLaunchKernelGGL((large_top_inv_kernel<N, K>), dim3(top_blocks(l)), dim3(TOPT), 0, Mst, la[l], c0[l], i);
-                }
-                if (i + 1 < a0.n) {
-                    TimedLaunch tl(a0.timer, "large_digits_kernel", Mst);
-                    hipLaunchKernelGGL(large_digits_kernel, dim3(dig_blocks(l)), dim3(LARGE_DIGT), 0, Mst, la[l], c0[l],
-                                       i + 1);
-                    (void)hipEventRecord(*dev[l], Mst);
-                }
-            }
-        }
-        for (int l = 0; l < lanes; l++) {
-            const size_t out_elems = (size_t)cnt[l] * (K * N + 1);
-            hipLaunchKernelGGL((large_extract_kernel<N, K>), dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, Mst,
-                               la[l], c0[l], cnt[l]);
-        }
-        // the next pair reuses both lanes' scratch: its init (lane_m) must follow this pair's last
-        // group kernels (lane_c) -- lane_m already ran top_inv after them (gA / gB waits above)
-    }
-    (void)hipEventRecord(gA, C);
-    (void)hipEventRecord(dA, Mst);
-    (void)hipStreamWaitEvent(s, gA, 0);
-    (void)hipStreamWaitEvent(s, dA, 0);
-    e = hipGetLastError();
-    for (auto &x : ev) (void)hipEventDestroy(x);
-    return e;
-}
-
 // The quad CMUX over the batch in passes of quad_pass ciphertexts.  Its workgroups wait on each
 // other, so two quad launches must never share the device's CUs: every launch of a device waits
 // for the previous one (an event chained across streams under a process-wide lock).
@@ -2987,29 +2625,160 @@ static hipError_t launch_quad(const LargePbsLaunch &a0, hipStream_t s) {
     return hipGetLastError();
 }
 
+// the whole blind rotation on chip, one workgroup per ciphertext, no scratch
+template <int N, int L>
+static hipError_t launch_onchip(const LargePbsLaunch &a, hipStream_t s) {
+    using Cfg = OnchipCfg<N>;
+    TimedLaunch tl(a.timer, "onchip_cmux_kernel", s);
+    const dim3 grid((unsigned)a.count), block(Cfg::THREADS);
+    if (a.base_log * L <= 30)  // 32-bit digit extraction (every shortint set at these shapes)
+        hipLaunchKernelGGL((onchip_cmux_kernel<N, true, L>), grid, block, Cfg::LDS, s, a);
+    else
+        hipLaunchKernelGGL((onchip_cmux_kernel<N, false, L>), grid, block, Cfg::LDS, s, a);
+    return hipGetLastError();
+}
+
+// The CMUXes of one chunk (a.chunk_count ciphertexts from ct0 on, accumulators initialised), one
+// function per sequence of launches.  Grids in whole rounds of 8 ciphertexts belong to the kernels
+// that place ciphertext cl on XCD cl % 8.
+static unsigned xcd_rounds(int cnt) { return (unsigned)((cnt + 7) / 8) * 8; }
+template <int K>
+static unsigned top_blocks(int cnt) { return (unsigned)cnt * (K + 1) * (1024 / TOPT); }
+
+// grouped CMUX (N = 32768, L = 2): digits, group kernel, top inverse
+static void launch_cmuxes_grouped(const LargePbsLaunch &a, int ct0, hipStream_t s) {
+    constexpr int N = LN, K = 1;
+    const int cnt = a.chunk_count;
+    const unsigned grp_blocks = xcd_rounds(cnt) * 4;
+    const unsigned dig_blocks = xcd_rounds(cnt) * (LM / LARGE_DIGT);
+    for (int i = 0; i < a.n; i++) {
+        {
+            TimedLaunch tl(a.timer, "large_digits_kernel", s);
+            hipLaunchKernelGGL(large_digits_kernel, dim3(dig_blocks), dim3(LARGE_DIGT), 0, s, a, ct0, i);
+        }
+        {
+            TimedLaunch tl(a.timer, "large_group_cmux_kernel", s);
+            hipLaunchKernelGGL(large_group_cmux_kernel, dim3(grp_blocks), dim3(GroupCfg::THREADS), GroupCfg::LDS, s, a,
+                               ct0, i);
+        }
+        TimedLaunch tl(a.timer, "large_top_inv_kernel", s);
+        hipLaunchKernelGGL((large_top_inv_kernel<N, K>), dim3(top_blocks<K>(cnt)), dim3(TOPT), 0, s, a, ct0, i);
+    }
+}
+
+// digits-fed CMUX (classic, L = 2, N = 4096 / 8192): digits once, then per CMUX the sub-blocks from
+// digits and the top inverse fused with the next CMUX's digits (a plain top inverse after the last).
+// At R = 8 the R-fold recomputation of the top stage in each sub-block workgroup costs more than the
+// spectra it saves (2_5: 2005 vs 2191 KS+PBS/s), so N = 16384 takes the generic split CMUX.
+template <int N>
+static void launch_cmuxes_digits_fed(const LargePbsLaunch &a, int ct0, hipStream_t s) {
+    using S = Split<N>;
+    using Sub = LargeSubCfg<1, 2>;
+    constexpr int K = 1;
+    const int cnt = a.chunk_count;
+    const unsigned dig_blocks = xcd_rounds(cnt) * (S::M / 256);
+    const unsigned dsub_blocks = xcd_rounds(cnt) * S::R;
+    const unsigned fused_blocks = xcd_rounds(cnt) * 2;  // (ct, row)
+    {
+        TimedLaunch tl(a.timer, "split_digits_kernel", s);
+        hipLaunchKernelGGL((split_digits_kernel<N>), dim3(dig_blocks), dim3(256), 0, s, a, ct0, 0);
+    }
+    for (int i = 0; i < a.n; i++) {
+        {
+            TimedLaunch tl(a.timer, "large_dsub_kernel", s);
+            hipLaunchKernelGGL((large_dsub_kernel<N>), dim3(dsub_blocks), dim3(Sub::THREADS), Sub::LDS, s, a, ct0, i);
+        }
+        if (i + 1 < a.n) {  // top_inv of CMUX i + digits of CMUX i + 1
+            TimedLaunch tl(a.timer, "split_inv_digits_kernel", s);
+            hipLaunchKernelGGL((split_inv_digits_kernel<N>), dim3(fused_blocks), dim3(1024), sizeof(acc_pair) * S::M, s,
+                               a, ct0, i);
+        } else {
+            TimedLaunch tl(a.timer, "large_top_inv_kernel", s);
+            hipLaunchKernelGGL((large_top_inv_kernel<N, K>), dim3(top_blocks<K>(cnt)), dim3(TOPT), 0, s, a, ct0, i);
+        }
+    }
+}
+
+// multi-bit (N = 8192, L = 2, g = 2 / 3): per group the paired sub-block kernel (3283 -> 8921
+// KS+PBS/s at PARAM_MULTI_BIT_MESSAGE_3_CARRY_3_GROUP_3 against large_sub_kernel) and the top inverse
+// fused with the next group's top stage; packed digits between the two from MB_DIGITS_MIN
+// ciphertexts on.  TFHE_MI355_MB_FUSED / _MB_PAIR2 / _MB_DIGITS=0 select the
+// separate launches, the pair kernel with monomials from the global table, the f64 spectra.
+template <int G>
+static void launch_cmuxes_multibit(const LargePbsLaunch &a, int ct0, hipStream_t s) {
+    constexpr int N = 8192, K = 1, L = 2;
+    using S = Split<N>;
+    using P2 = MbPair2Cfg<N, G>;
+    using PairSub = PairSubCfg<K, L>;
+    const int cnt = a.chunk_count;
+    const unsigned fwd_blocks = xcd_rounds(cnt) * (K + 1) * (1024 / TOPT);
+    const dim3 pair_grid(pair_sub_blocks<S::R>((cnt + 1) / 2));
+    const int steps = a.n / G;
+    const bool fused = mb_fused_enabled(), pair2 = mb_pair2_enabled();
+    const bool dig = fused && pair2 && mb_digits_enabled(cnt) && a.base_log * 2 <= 30;
+    for (int i = 0; i < steps; i++) {
+        if (i == 0 && dig) {
+            TimedLaunch tl(a.timer, "mb_digits_init_kernel", s);
+            hipLaunchKernelGGL((mb_digits_init_kernel<N>), dim3((unsigned)cnt * 8), dim3(256), 0, s, a, ct0);
+        } else if (i == 0 || !fused) {
+            TimedLaunch tl(a.timer, "large_top_fwd_kernel", s);
+            hipLaunchKernelGGL((large_top_fwd_kernel<N, K, L, G>), dim3(fwd_blocks), dim3(TOPT), 0, s, a, ct0, i);
+        }
+        if (pair2) {  // monomials from LDS
+            TimedLaunch tl(a.timer, "large_mb_pair2_kernel", s);
+            if (dig)
+                hipLaunchKernelGGL((large_mb_pair2_kernel<N, G, true>), pair_grid, dim3(P2::THREADS), P2::LDS, s, a, ct0, i);
+            else
+                hipLaunchKernelGGL((large_mb_pair2_kernel<N, G, false>), pair_grid, dim3(P2::THREADS), P2::LDS, s, a, ct0, i);
+        } else {
+            TimedLaunch tl(a.timer, "large_pair_sub_kernel", s);
+            hipLaunchKernelGGL((large_pair_sub_kernel<N, K, L, G, 1>), pair_grid, dim3(PairSub::THREADS), PairSub::LDS, s,
+                               a, ct0, i);
+        }
+        if (fused && i + 1 < steps) {  // top_inv of group i + top_fwd (or digits) of group i + 1
+            TimedLaunch tl(a.timer, "large_mb_inv_fwd_kernel", s);
+            if (dig)
+                hipLaunchKernelGGL((large_mb_inv_fwd_kernel<N, K, L, G, true>), dim3(fwd_blocks), dim3(TOPT), 0, s, a, ct0, i);
+            else
+                hipLaunchKernelGGL((large_mb_inv_fwd_kernel<N, K, L, G, false>), dim3(fwd_blocks), dim3(TOPT), 0, s, a, ct0, i);
+        } else {
+            TimedLaunch tl(a.timer, "large_top_inv_kernel", s);
+            hipLaunchKernelGGL((large_top_inv_kernel<N, K, G>), dim3(top_blocks<K>(cnt)), dim3(TOPT), 0, s, a, ct0, i);
+        }
+    }
+}
+
+// generic split CMUX: top stage, sub-blocks, top inverse (large_pair_sub_kernel measured slower
+// than large_sub_kernel for the classic sets: 4640 vs 4895 KS+PBS/s at 3_3, 939 vs 1036 at 4_4 split)
+template <int N, int K, int L>
+static void launch_cmuxes_split(const LargePbsLaunch &a, int ct0, hipStream_t s) {
+    using Sub = LargeSubCfg<K, L>;
+    const int cnt = a.chunk_count;
+    const unsigned fwd_blocks = xcd_rounds(cnt) * (K + 1) * (1024 / TOPT);
+    const unsigned sub_blocks = (unsigned)cnt * Split<N>::R;
+    for (int i = 0; i < a.n; i++) {
+        {
+            TimedLaunch tl(a.timer, "large_top_fwd_kernel", s);
+            hipLaunchKernelGGL((large_top_fwd_kernel<N, K, L, 0>), dim3(fwd_blocks), dim3(TOPT), 0, s, a, ct0, i);
+        }
+        {
+            TimedLaunch tl(a.timer, "large_sub_kernel", s);
+            hipLaunchKernelGGL((large_sub_kernel<N, K, L>), dim3(sub_blocks), dim3(Sub::THREADS), Sub::LDS, s, a, ct0, i);
+        }
+        TimedLaunch tl(a.timer, "large_top_inv_kernel", s);
+        hipLaunchKernelGGL((large_top_inv_kernel<N, K>), dim3(top_blocks<K>(cnt)), dim3(TOPT), 0, s, a, ct0, i);
+    }
+}
+
 template <int N, int K, int L, int G = 0>
 static hipError_t launch_large_t(const LargePbsLaunch &a0, hipStream_t s) {
     using S = Split<N>;
     if (a0.count == 0) return hipSuccess;
-    if constexpr (G == 0 && K == 1 && (L == 2 || L == 1) && (S::R == 4 || S::R == 2)) {  // quad (8192) / duo (4096)
+    if constexpr (G == 0 && K == 1 && L <= 2 && S::R <= 4) {  // N = 8192 (quad) / 4096 (duo)
         if (quad_enabled() && a0.count <= a0.quad_max_count) return launch_quad<N, L>(a0, s);
-    }
-    if constexpr (G == 0 && K == 1 && (L == 2 || L == 1) && (S::R == 4 || S::R == 2)) {
-        if (onchip_enabled() && a0.count >= a0.onchip_min_count) {  // the whole blind rotation on chip, no scratch
-            TimedLaunch tl(a0.timer, "onchip_cmux_kernel", s);
-            const dim3 grid((unsigned)((a0.count + OnchipCfg<N>::CPW - 1) / OnchipCfg<N>::CPW)), block(OnchipCfg<N>::THREADS);
-            if (a0.base_log * L <= 30)  // 32-bit digit extraction (every shortint set at these shapes)
-                hipLaunchKernelGGL((onchip_cmux_kernel<N, true, L>), grid, block, OnchipCfg<N>::LDS, s, a0);
-            else
-                hipLaunchKernelGGL((onchip_cmux_kernel<N, false, L>), grid, block, OnchipCfg<N>::LDS, s, a0);
-            return hipGetLastError();
-        }
+        if (onchip_enabled() && a0.count >= a0.onchip_min_count) return launch_onchip<N, L>(a0, s);
     }
     const size_t per_ct = large_pbs_scratch_per_ct(N, K, L);
-    if constexpr (N == LN && K == 1 && L == 2 && G == 0) {
-        if (LARGE_GROUP_SUB && large_grouped_enabled() && a0.lane_c && a0.lane_m)
-            return launch_grouped_lanes(a0, s, per_ct);
-    }
     const int chunk = (int)std::min<size_t>((size_t)a0.count, a0.scratch_bytes / per_ct);
     if (chunk <= 0) return hipErrorInvalidValue;
     LargePbsLaunch a = a0;
@@ -3023,141 +2792,11 @@ static hipError_t launch_large_t(const LargePbsLaunch &a0, hipStream_t s) {
         const size_t init_elems = (size_t)cnt * (K + 1) * N;
         hipLaunchKernelGGL((large_init_kernel<N, K>), dim3((unsigned)((init_elems + 255) / 256)), dim3(256), 0, s, a,
                            ct0, cnt);
-        using Sub = LargeSubCfg<K, L>;
-        const unsigned top_blocks = (unsigned)cnt * (K + 1) * (1024 / TOPT);
-        const unsigned fwd_blocks = (unsigned)((cnt + 7) / 8) * 8 * (K + 1) * (1024 / TOPT);
+        if constexpr (G > 0) launch_cmuxes_multibit<G>(a, ct0, s);
+        else if constexpr (N == LN && K == 1 && L == 2) launch_cmuxes_grouped(a, ct0, s);
+        else if constexpr (K == 1 && L == 2 && S::R <= 4) launch_cmuxes_digits_fed<N>(a, ct0, s);
+        else launch_cmuxes_split<N, K, L>(a, ct0, s);
         const size_t out_elems = (size_t)cnt * (K * N + 1);
-        if constexpr (N == LN && K == 1 && L == 2 && G == 0) {
-            if (LARGE_GROUP_SUB && large_grouped_enabled()) {
-                const unsigned grp_blocks = (unsigned)((cnt + 7) / 8) * 8 * 4 * GroupCfg::PARTS;
-                const unsigned dig_blocks = (unsigned)((cnt + 7) / 8) * 8 * (LM / LARGE_DIGT);
-                for (int i = 0; i < a.n; i++) {
-                    {
-                        TimedLaunch tl(a.timer, "large_digits_kernel", s);
-                        hipLaunchKernelGGL(large_digits_kernel, dim3(dig_blocks), dim3(LARGE_DIGT), 0, s, a, ct0, i);
-                    }
-                    {
-                        TimedLaunch tl(a.timer, "large_group_cmux_kernel", s);
-                        hipLaunchKernelGGL(large_group_cmux_kernel, dim3(grp_blocks), dim3(GroupCfg::THREADS),
-                                           GroupCfg::LDS, s, a, ct0, i);
-                    }
-                    TimedLaunch tl(a.timer, "large_top_inv_kernel", s);
-                    hipLaunchKernelGGL((large_top_inv_kernel<N, K>), dim3(top_blocks), dim3(TOPT), 0, s, a, ct0, i);
-                }
-                hipLaunchKernelGGL((large_extract_kernel<N, K>), dim3((unsigned)((out_elems + 255) / 256)), dim3(256),
-                                   0, s, a, ct0, cnt);
-                continue;
-            }
-        }
-        // N = 4096 / 8192 only: at R = 8 the R-fold recomputation of the top stage in each
-        // sub-block workgroup costs more than the spectra it saves (2_5: 2005 vs 2191 KS+PBS/s)
-        if constexpr (G == 0 && K == 1 && L == 2 && S::R <= 4) {
-            if (large_dsub_enabled()) {  // digits-fed CMUX: digits, sub-blocks from digits, top_inv
-                constexpr int DPER = S::M / 256;
-                const unsigned dig_blocks = (unsigned)((cnt + 7) / 8) * 8 * DPER;
-                const unsigned dsub_blocks = (unsigned)((cnt + 7) / 8) * 8 * S::R;
-                const unsigned fused_blocks = (unsigned)((cnt + 7) / 8) * 8 * 2;  // (ct, row)
-                const bool fused = split_fused_enabled();
-                for (int i = 0; i < a.n; i++) {
-                    if (i == 0 || !fused) {
-                        TimedLaunch tl(a.timer, "split_digits_kernel", s);
-                        hipLaunchKernelGGL((split_digits_kernel<N>), dim3(dig_blocks), dim3(256), 0, s, a, ct0, i);
-                    }
-                    {
-                        TimedLaunch tl(a.timer, "large_dsub_kernel", s);
-                        hipLaunchKernelGGL((large_dsub_kernel<N>), dim3(dsub_blocks), dim3(Sub::THREADS), Sub::LDS, s,
-                                           a, ct0, i);
-                    }
-                    if (fused && i + 1 < a.n) {  // top_inv of CMUX i + digits of CMUX i + 1
-                        TimedLaunch tl(a.timer, "split_inv_digits_kernel", s);
-                        hipLaunchKernelGGL((split_inv_digits_kernel<N>), dim3(fused_blocks), dim3(1024),
-                                           sizeof(acc_pair) * S::M, s, a, ct0, i);
-                        continue;
-                    }
-                    TimedLaunch tl(a.timer, "large_top_inv_kernel", s);
-                    hipLaunchKernelGGL((large_top_inv_kernel<N, K, G>), dim3(top_blocks), dim3(TOPT), 0, s, a, ct0, i);
-                }
-                hipLaunchKernelGGL((large_extract_kernel<N, K>), dim3((unsigned)((out_elems + 255) / 256)), dim3(256),
-                                   0, s, a, ct0, cnt);
-                continue;
-            }
-        }
-        const unsigned sub_blocks = (unsigned)cnt * S::R;
-        const int steps = G ? a.n / G : a.n;  // CMUXes, or multi-bit groups
-        const bool mb_fused = G > 0 && mb_fused_enabled();  // top_inv of group i + top_fwd of i + 1
-        // packed digits between the fused inverse and the pair kernel (MB2_DIGITS)
-        const bool mb_dig = N == 8192 && K == 1 && L == 2 && mb_fused && mb_pair2_enabled() && mb_digits_enabled(cnt) &&
-                            a.base_log * 2 <= 30;
-        for (int i = 0; i < steps; i++) {
-            if (i == 0 && mb_dig) {
-                TimedLaunch tl(a.timer, "mb_digits_init_kernel", s);
-                hipLaunchKernelGGL((mb_digits_init_kernel<N>), dim3((unsigned)cnt * 8), dim3(256), 0, s, a, ct0);
-            } else if (i == 0 || !mb_fused) {
-                TimedLaunch tl(a.timer, "large_top_fwd_kernel", s);
-                hipLaunchKernelGGL((large_top_fwd_kernel<N, K, L, G>), dim3(fwd_blocks), dim3(TOPT), 0, s, a, ct0, i);
-            }
-            if constexpr (G > 0) {
-                // multi-bit: the paired kernel (3283 -> 8921 KS+PBS/s at
-                // PARAM_MULTI_BIT_MESSAGE_3_CARRY_3_GROUP_3; for the classic sets it measured slower
-                // than large_sub_kernel: 4640 vs 4895 KS+PBS/s at 3_3, 939 vs 1036 at 4_4 split)
-                using PairSub = PairSubCfg<K, L>;
-                bool pair2 = false;
-                if constexpr (N == 8192 && K == 1 && L == 2) {  // monomials from LDS (large_mb_pair2_kernel)
-                    if (mb_pair2_enabled()) {
-                        using P2 = MbPair2Cfg<N, G>;
-                        TimedLaunch tl(a.timer, "large_mb_pair2_kernel", s);
-                        if (mb_dig)
-                            hipLaunchKernelGGL((large_mb_pair2_kernel<N, G, true>), dim3(pair_sub_blocks<S::R>((cnt + 1) / 2)),
-                                               dim3(P2::THREADS), P2::LDS, s, a, ct0, i);
-                        else
-                            hipLaunchKernelGGL((large_mb_pair2_kernel<N, G, false>), dim3(pair_sub_blocks<S::R>((cnt + 1) / 2)),
-                                               dim3(P2::THREADS), P2::LDS, s, a, ct0, i);
-                        pair2 = true;
-                    }
-                }
-                if (!pair2) {
-                    TimedLaunch tl(a.timer, "large_pair_sub_kernel", s);
-                    hipLaunchKernelGGL((large_pair_sub_kernel<N, K, L, G, 1>), dim3(pair_sub_blocks<S::R>((cnt + 1) / 2)),
-                                       dim3(PairSub::THREADS), PairSub::LDS, s, a, ct0, i);
-                }
-            } else {
-                bool paired = false;
-                if constexpr (16 % (2 * (K + 1) * L) == 0) {  // L <= 2 at k = 1
-                    if (large_pair_sub_classic()) {
-                        using PairSub = PairSubCfg<K, L>;
-                        TimedLaunch tl(a.timer, "large_pair_sub_kernel", s);
-                        hipLaunchKernelGGL((large_pair_sub_kernel<N, K, L, G, 1>),
-                                           dim3(pair_sub_blocks<S::R>((cnt + 1) / 2)), dim3(PairSub::THREADS),
-                                           PairSub::LDS, s, a, ct0, i);
-                        paired = true;
-                    }
-                }
-                if (!paired) {
-                    TimedLaunch tl(a.timer, "large_sub_kernel", s);
-                    hipLaunchKernelGGL((large_sub_kernel<N, K, L>), dim3(sub_blocks), dim3(Sub::THREADS), Sub::LDS, s,
-                                       a, ct0, i);
-                }
-            }
-            if constexpr (G > 0) {
-                if (mb_fused && i + 1 < steps) {
-                    TimedLaunch tl(a.timer, "large_mb_inv_fwd_kernel", s);
-                    bool dig_done = false;
-                    if constexpr (N == 8192 && K == 1 && L == 2) {
-                        if (mb_dig) {
-                            hipLaunchKernelGGL((large_mb_inv_fwd_kernel<N, K, L, G, true>), dim3(fwd_blocks), dim3(TOPT), 0,
-                                               s, a, ct0, i);
-                            dig_done = true;
-                        }
-                    }
-                    if (!dig_done)
-                        hipLaunchKernelGGL((large_mb_inv_fwd_kernel<N, K, L, G, false>), dim3(fwd_blocks), dim3(TOPT), 0,
-                                           s, a, ct0, i);
-                    continue;
-                }
-            }
-            TimedLaunch tl(a.timer, "large_top_inv_kernel", s);
-            hipLaunchKernelGGL((large_top_inv_kernel<N, K, G>), dim3(top_blocks), dim3(TOPT), 0, s, a, ct0, i);
-        }
         hipLaunchKernelGGL((large_extract_kernel<N, K>), dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, s, a,
                            ct0, cnt);
     }
