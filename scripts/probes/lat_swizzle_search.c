@@ -1,5 +1,5 @@
 // Exhaustive search for an XOR swizzle of the latency kernel's exchange buffers (pbs_latency.hip,
-// LAT_MAP = 1 lane mapping): slot(P) = P ^ f(P >> 4) with f a linear map of bits 4..9 onto bits
+// three-barrier lane mapping): slot(P) = P ^ f(P >> 4) with f a linear map of bits 4..9 onto bits
 // 0..3 (4 x 6 GF(2) matrix, 2^24 candidates).  A candidate is accepted when every access pattern
 // of a wave is free of bank conflicts for both ds_read_b128's 16-lane groups (16-byte slot =
 // P' mod 16) and ds_write_b128's 8-lane groups (P' mod 8):

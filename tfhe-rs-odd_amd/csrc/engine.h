@@ -143,6 +143,11 @@ hipError_t launch_classic_pbs(int N, int k, int L, const ClassicPbsLaunch &a, hi
 // batches (the one-ciphertext-per-call pattern).  N = 2048, k = 1, L = 1 only; no ticket, no scratch.
 bool latency_pbs_supported(int N, int k, int L);
 hipError_t launch_latency_pbs(const ClassicPbsLaunch &a, hipStream_t s);
+// diagnostic builds: the latency kernel writes s_memtime per CMUX phase of block 0 into the buffer
+// the host passes as `ticket` (capi.cpp), read by scripts/latency_probe.py
+#ifndef LAT_STAMPS
+#define LAT_STAMPS 0
+#endif
 
 struct MultiBitPbsLaunch {
     const uint64_t *lwe_in;      // [count][n+1]

@@ -189,27 +189,9 @@ __device__ __forceinline__ cx lds_ld(const cx *xb, int p) {
     double2 t = reinterpret_cast<const double2 *>(xb)[xpad(p)];
     return {t.x, t.y};
 }
-// M = 1024 exchange addressing.  Default: one pad slot per 64 positions (p + p/64): both access
-// patterns (lane + 64 c, and 64 cc + a1 + 4 b) become a per-lane base + compile-time immediate
-// offsets.  TM_XCHG_XOR=1: unpadded buffer with an XOR swizzle of the 16-B slot,
-// p ^ ((p >> 6) & 15) (saves 256 B per buffer, costs per-access address math).
-#ifndef TM_TW_SB
-#define TM_TW_SB 16 // twiddle multiplies per scheduling region (16 = one region)
-#endif
-#ifndef TM_XCHG_XOR
-#define TM_XCHG_XOR 1
-#endif
-__device__ __forceinline__ int xswz(int p) { return TM_XCHG_XOR ? (p ^ ((p >> 6) & 15)) : xpad(p); }
-constexpr int xbuf_len_1024() { return TM_XCHG_XOR ? 1024 : xbuf_len(1024); }
-__device__ __forceinline__ void lds_stx(cx *xb, int p, cx v) {
-    reinterpret_cast<double2 *>(xb)[xswz(p)] = make_double2(v.re, v.im);
-}
-__device__ __forceinline__ cx lds_ldx(const cx *xb, int p) {
-    double2 t = reinterpret_cast<const double2 *>(xb)[xswz(p)];
-    return {t.x, t.y};
-}
-// M = 1024 XOR-swizzled exchange on byte addresses: for a buffer at a 1 KiB-aligned LDS address
-// X, 16 xswz(p) + X is
+// M = 1024 exchange addressing: an unpadded buffer (1024 slots) with an XOR swizzle of the 16-B
+// slot, xswz(p) = p ^ ((p >> 6) & 15), on byte addresses.  For a buffer at a 1 KiB-aligned LDS
+// address X, 16 xswz(p) + X is
 //   p = lane + 64 c        : ((X + 16 lane) ^ 16 c) + 1024 c   (one v_xor; 1024 c is the ds offset)
 //   p = 64 cc + a1 + 4 b   : (X + 1024 cc + 16 (a1 ^ cc)) ^ 64 b (one v_xor)
 // since X has no bits in 4..9 and (a1 + 4 b) ^ cc = (a1 ^ cc) ^ 4 b (a1 < 4).
@@ -363,7 +345,8 @@ template <>
 struct WaveFft<1024> {
     static constexpr int M = 1024;
     static constexpr int V = 16;
-    static constexpr int XL = xbuf_len_1024();  // exchange buffer entries
+    static constexpr int XL = 1024;  // exchange buffer entries (unpadded: XOR-swizzled slots)
+    static constexpr int TW_SB = 16;  // twiddle multiplies per scheduling region (16 = one region)
     using Lds = LdsTwiddles<16, 16, 4>;
     // Spectrum element (slot s, lane) sits at FFT position P = 64 (lane & 15) + 16 (lane >> 4) + s;
     // the DIF output is digit reversed (P = 64 c0 + 4 c1 + c2 -> f = c0 + 16 c1 + 256 c2), so its
@@ -377,32 +360,24 @@ struct WaveFft<1024> {
         dft16_fwd(v);
 #pragma unroll
         for (int c = 1; c < 16; c++) {
-            if (c % TM_TW_SB == 1) __builtin_amdgcn_sched_barrier(0);  // bound twiddle loads in flight
+            if (c % TW_SB == 1) __builtin_amdgcn_sched_barrier(0);  // bound twiddle loads in flight
             cx w = tw.s1(c, lane);
             v[c] = cmulw(v[c], w.re, w.im);
         }
         sync();  // previous readers of xb done
         const int cc = lane & 15, a1 = lane >> 4;
-        if constexpr (TM_XCHG_XOR) {
-            const uint32_t xa = lds_addr(xb), la = launder_addr<Sync, 1>(xa + 16u * lane);
+        const uint32_t xa = lds_addr(xb), la = launder_addr<Sync, 1>(xa + 16u * lane);
 #pragma unroll
-            for (int c = 0; c < 16; c++) lds_st_at((la ^ (16u * c)) + 1024u * c, v[c]);
-            sync();
-            // stage 2: blocks of 64 (cc), R=16, m=4 (a1 = row)
-            const uint32_t qa = launder_addr<Sync, 2>(xa + 1024u * cc + 16u * (a1 ^ cc));
+        for (int c = 0; c < 16; c++) lds_st_at((la ^ (16u * c)) + 1024u * c, v[c]);
+        sync();
+        // stage 2: blocks of 64 (cc), R=16, m=4 (a1 = row)
+        const uint32_t qa = launder_addr<Sync, 2>(xa + 1024u * cc + 16u * (a1 ^ cc));
 #pragma unroll
-            for (int b = 0; b < 16; b++) v[b] = lds_ld_at(qa ^ (64u * b));
-        } else {
-#pragma unroll
-            for (int c = 0; c < 16; c++) lds_stx(xb, lane + 64 * c, v[c]);
-            sync();
-#pragma unroll
-            for (int b = 0; b < 16; b++) v[b] = lds_ldx(xb, 64 * cc + a1 + 4 * b);
-        }
+        for (int b = 0; b < 16; b++) v[b] = lds_ld_at(qa ^ (64u * b));
         dft16_fwd(v);
 #pragma unroll
         for (int c2 = 1; c2 < 16; c2++) {
-            if (c2 % TM_TW_SB == 1) __builtin_amdgcn_sched_barrier(0);
+            if (c2 % TW_SB == 1) __builtin_amdgcn_sched_barrier(0);
             cx w = tw.s2(c2, a1);
             v[c2] = cmulw(v[c2], w.re, w.im);
         }
@@ -445,31 +420,18 @@ struct WaveFft<1024> {
         }
         dft16_inv(v);
         sync();  // previous readers of xb done
-        if constexpr (TM_XCHG_XOR) {
-            const uint32_t xa = lds_addr(xb);
-            const uint32_t qa = launder_addr<Sync, 2>(xa + 1024u * cc + 16u * (a1 ^ cc));
+        const uint32_t xa = lds_addr(xb);
+        const uint32_t qa = launder_addr<Sync, 2>(xa + 1024u * cc + 16u * (a1 ^ cc));
 #pragma unroll
-            for (int b = 0; b < 16; b++) lds_st_at(qa ^ (64u * b), v[b]);
-            sync();
-            const uint32_t la = launder_addr<Sync, 1>(xa + 16u * lane);
-            v[0] = lds_ld_at(la);
+        for (int b = 0; b < 16; b++) lds_st_at(qa ^ (64u * b), v[b]);
+        sync();
+        const uint32_t la = launder_addr<Sync, 1>(xa + 16u * lane);
+        v[0] = lds_ld_at(la);
 #pragma unroll
-            for (int c = 1; c < 16; c++) {
-                cx y = lds_ld_at((la ^ (16u * c)) + 1024u * c);
-                cx w = tw.s1(c, lane);
-                v[c] = cmulw(y, w.re, -w.im);
-            }
-        } else {
-#pragma unroll
-            for (int b = 0; b < 16; b++) lds_stx(xb, 64 * cc + a1 + 4 * b, v[b]);
-            sync();
-            v[0] = lds_ldx(xb, lane);
-#pragma unroll
-            for (int c = 1; c < 16; c++) {
-                cx y = lds_ldx(xb, lane + 64 * c);
-                cx w = tw.s1(c, lane);
-                v[c] = cmulw(y, w.re, -w.im);
-            }
+        for (int c = 1; c < 16; c++) {
+            cx y = lds_ld_at((la ^ (16u * c)) + 1024u * c);
+            cx w = tw.s1(c, lane);
+            v[c] = cmulw(y, w.re, -w.im);
         }
         dft16_inv(v);
     }

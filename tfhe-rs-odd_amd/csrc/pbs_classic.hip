@@ -33,31 +33,14 @@
 #include "pbs_common.h"
 #include "rot_mask.h"
 
-#ifndef CLASSIC_DIGIT2
-#define CLASSIC_DIGIT2 1  // L = 2 shapes: Digit2 (pbs_common.h) instead of the per-level digit loop (0: A/B)
-#endif
-
 namespace tfhe_mi355 {
 
-#ifndef PBS_CPW
-#define PBS_CPW 0  // ciphertexts per workgroup; 0: per-shape default
-#endif
 #ifndef PBS_TSKIP_ROT
 #define PBS_TSKIP_ROT 0  // timing-only builds (wrong outputs): no rotation gather (what the rotation costs)
-#endif
-#ifndef PBS_GGSW_LDS
-#define PBS_GGSW_LDS 0  // measured 2% slower than streaming from L2 (CPW=2 couples 4 waves); kept as an option
-#endif
-#ifndef PBS_ROT_GROUP
-#define PBS_ROT_GROUP 1  // L = 1: slots whose rotation gathers are issued as one group ahead of use (0: none)
-#endif
-#ifndef PBS_ROT_AHEAD
-#define PBS_ROT_AHEAD 1  // groups in flight ahead of the one being consumed
 #endif
 template <int N, int K, int L>
 struct PbsConfig {
     static constexpr int M = N / 2;
-    static constexpr size_t GGSW_ELEMS = (size_t)L * (K + 1) * (K + 1) * M;  // double2 per GGSW
     // 2_2 shape (N = 2048, k = 1, L = 1): 4 ciphertexts per workgroup at 2 waves/SIMD.  The MAC
     // reads every row spectrum back from LDS (the own row's 64 VGPRs are free by then: 226
     // VGPRs, no spills) and the twist/M table is dropped, so 31 KiB of tables + 8 x 16 KiB
@@ -67,21 +50,18 @@ struct PbsConfig {
     // kept in registers: frees the own row's VGPRs.  Per shape (measured, gadget sets): on at
     // N = 2048 (PACK4) and N = 1024 (TFHE_LIB 93.7k -> 109.3k, ASCON_40 34.3k -> 37.4k,
     // MANTICORE +2%), off at N = 512 (SIMON_40 -3%, AES_40 -5%: no spills to remove there)
-    static constexpr bool MAC_LDS = PBS_MAC_FROM_LDS >= 0 ? (bool)PBS_MAC_FROM_LDS : (PACK4 || N == 1024);
-    // GGSW_i staged in LDS by async global->LDS loads and shared by the workgroup's ciphertexts;
-    // fits next to the tables and 2 x (k+1) exchange buffers when it is <= 64 KiB
-    // (only without the twist/M table: both do not fit next to four exchange buffers)
-    static constexpr bool STAGE = PBS_GGSW_LDS && !PACK4 && GGSW_ELEMS * 16 <= 65536;
-    static constexpr int CPW = PBS_CPW > 0 ? PBS_CPW : STAGE ? 2 : PACK4 ? 4 : 1;
-    static constexpr bool GSYNC = PBS_GROUP_SYNC && !STAGE;  // the staged GGSW is shared by the workgroup
-    static constexpr size_t flags_off() { return PbsLds<M>::bytes((K + 1) * CPW) + (STAGE ? GGSW_ELEMS * 16 : 0); }
-    static constexpr size_t lds_bytes() { return flags_off() + (GSYNC ? 4 * (K + 1) * CPW + 4 * CPW : 0); }
+    static constexpr bool MAC_LDS = PACK4 || N == 1024;
+    static constexpr int CPW = PACK4 ? 4 : 1;  // ciphertexts per workgroup
+    // after the exchange buffers: one GroupSync flag word per wave, then one ticket word per slot
+    static constexpr size_t flags_off() { return PbsLds<M>::bytes((K + 1) * CPW); }
+    static constexpr size_t ticket_off() { return flags_off() + 4 * (K + 1) * CPW; }
+    static constexpr size_t lds_bytes() { return ticket_off() + 4 * CPW; }
     static_assert(lds_bytes() <= 160 * 1024, "LDS per workgroup exceeds a CU");
     // register budget per wave: 2 waves/SIMD for the packed 2_2 shape and N = 1024 (<= 256),
     // 3 at N = 512 (<= 168), 1 for the other N = 2048 shapes (~430 VGPR+AGPR at L = 2)
-    static constexpr int WPE = PBS_WAVES_PER_EU > 0 ? PBS_WAVES_PER_EU
-                                                    : (PACK4 ? 2 : N >= 2048 ? 1 : N == 1024 ? 2 : 3);
-    // Persistent grid with a dynamic ciphertext queue (needs GSYNC: slots never wait on each other).
+    static constexpr int WPE = PACK4 ? 2 : N >= 2048 ? 1 : N == 1024 ? 2 : 3;
+    // Persistent grid with a dynamic ciphertext queue (the per-ciphertext GroupSync means slots
+    // never wait on each other).
     // With one ciphertext per slot and launch, a workgroup holds its CU until its slowest slot is
     // done; its ciphertexts drift apart (per-ciphertext sync), so on average only 1.6 of the 2
     // waves per SIMD are resident (PMC).  Here a slot that finishes takes the next ciphertext from
@@ -90,12 +70,10 @@ struct PbsConfig {
     // waves/SIMD at 2_2): 2_2 115.0k -> 125.3k PBS/s, 2_2 KS+PBS 111.4k -> 121.2k, MANTICORE
     // 98.0k -> 108.7k, SHA3_40 99.3k -> 114.8k, ASCON_40 37.3k -> 40.6k; slower for TFHE_LIB
     // (1024, 2, 1) 108.9k -> 104.5k and SIMON_40 (512, 3, 2) 97.5k -> 91.9k, even for AES_40:
-    // on for the shapes where it measured faster (PBS_PERSIST = 0/1 forces it off/on).
-    static constexpr bool PERSIST_DEFAULT =
+    // on for the shapes where it measured faster.
+    static constexpr bool PERSIST =
         (N == 2048 && K == 1 && L == 1) || (N == 1024 && K == 1 && L == 2) || (N == 256 && K == 5 && L == 1) ||
         (N == 1024 && K == 2 && L == 3);
-    static constexpr bool PERSIST = GSYNC && (PBS_PERSIST >= 0 ? (bool)PBS_PERSIST : PERSIST_DEFAULT);
-    static constexpr size_t ticket_off() { return flags_off() + (GSYNC ? 4 * (K + 1) * CPW : 0); }
 };
 
 template <int N, int K, int L>
@@ -106,7 +84,6 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
     constexpr int LOG2N = ilog2(N);
     using Cfg = PbsConfig<N, K, L>;
     constexpr int CPW = Cfg::CPW;
-    constexpr bool STAGE = Cfg::STAGE;
     using Fft = WaveFft<M>;
     using Lay = PbsLds<M>;
     constexpr int XL = Lay::XL;
@@ -119,36 +96,27 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
     // wave-uniform ids in SGPRs: per-ciphertext pointers and the mask element loads stay scalar
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane0 = threadIdx.x & 63;
-    // wave -> (ciphertext slot, polynomial).  PBS_SLOT_MAJOR: wave w = r CPW + slot, so with the
-    // workgroup's waves placed round-robin on the CU's 4 SIMDs each SIMD hosts the (k+1) waves of
-    // ONE ciphertext (CPW = 4, k = 1) instead of rows of two different ciphertexts
-    const int wave = PBS_SLOT_MAJOR ? wid / CPW : wid % (K + 1);  // polynomial of the ciphertext this wave owns
-    const int slot = PBS_SLOT_MAJOR ? wid % CPW : wid / (K + 1);  // ciphertext slot in the workgroup
+    const int wave = wid % (K + 1);  // polynomial of the ciphertext this wave owns
+    const int slot = wid / (K + 1);  // ciphertext slot in the workgroup
     const int n = a.n;
     const int beta = a.base_log;
     const uint32_t dmask = (1u << beta) - 1;
     const DigitL1 digit_l1(beta);                      // L = 1 digits
     const Digit2 digit2(L == 2 ? beta : 2);             // L = 2: both levels of a pair at once (2 beta <= 30)
-    BlockSync sync;       // cross-wave: spectrum exchange
-#if PBS_WAVE_LOCAL
+    BlockSync sync;       // whole workgroup: table fill
     WaveLocalSync wsync;  // wave-private buffer reuse
-#else
-    BlockSync wsync;
-#endif
 
     // twiddles and twist -> LDS (once per workgroup)
     for (int e = threadIdx.x; e < M; e += blockDim.x) lds[Lay::twist_off + e] = a.twist[e];
     uint32_t *gflags = reinterpret_cast<uint32_t *>(smem + Cfg::flags_off());
-    if (Cfg::GSYNC && threadIdx.x < (K + 1) * CPW) gflags[threadIdx.x] = 0;
+    if (threadIdx.x < (K + 1) * CPW) gflags[threadIdx.x] = 0;
     Fft::Lds::template fill<M>(lds + Lay::s1_off, lds + Lay::s2_off, a.W, threadIdx.x, blockDim.x);
     const typename Fft::Lds tw{lds + Lay::s1_off, lds + Lay::s2_off};
     sync();  // tables visible to every wave (the CMUX loop itself only syncs wave-locally)
 
     cx *xct = reinterpret_cast<cx *>(lds + Lay::xbuf_off) + (size_t)slot * (K + 1) * XL;  // this ct's buffers
     // spectrum exchange among this ciphertext's waves
-    std::conditional_t<Cfg::GSYNC, GroupSync<K + 1>, BlockSync> xsync;
-    if constexpr (Cfg::GSYNC)
-        xsync = {lds_addr(gflags + slot * (K + 1)), lds_addr(gflags + slot * (K + 1) + wave)};
+    GroupSync<K + 1> xsync{lds_addr(gflags + slot * (K + 1)), lds_addr(gflags + slot * (K + 1) + wave)};
     cx *xb = xct + wave * XL;
     uint64_t *xb64 = reinterpret_cast<uint64_t *>(xb);
 
@@ -195,47 +163,6 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
 
     constexpr size_t ggsw_stride = (size_t)L * (K + 1) * (K + 1) * M;
     const double2 *gcol = A.fbsk + (size_t)wave * M + lane;  // column c = wave, this lane
-    // staged GGSW: LDS image identical to the global one (lane-linear 1 KiB chunks)
-    double2 *s_ggsw = lds + Lay::xbuf_off + (size_t)CPW * (K + 1) * XL;
-    // The LDS-DMA is issued from inline asm: issued through the builtin, hipcc makes every later
-    // LDS read wait vmcnt(0) (it cannot prove the DMA target disjoint), which drains the prefetch
-    // at the first FFT twiddle read.  Hidden from it, the copy is retired explicitly before the
-    // barrier that precedes its reader (stage_ggsw_wait); the loop issues no other vector loads.
-    const uint32_t s_ggsw_addr = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)(s_ggsw));
-    auto stage_ggsw = [&](int i) {
-        const double2 *src = A.fbsk + (size_t)i * ggsw_stride + lane0;
-        for (int q = wid; q < (int)(ggsw_stride / 64); q += CPW * (K + 1)) {
-            const uint32_t dst = __builtin_amdgcn_readfirstlane(s_ggsw_addr + (uint32_t)q * 1024u);
-            uint32_t keep;
-            asm volatile(
-                "s_mov_b32 %0, m0\n\t"
-                "s_mov_b32 m0, %2\n\t"
-                "s_nop 0\n\t"
-                "global_load_lds_dwordx4 %1, off\n\t"
-                "s_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "v"(src + q * 64), "s"(dst)
-                : "memory");
-        }
-    };
-    auto stage_ggsw_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-    if constexpr (STAGE) stage_ggsw(0);  // drained by the first spectrum-publish barrier
-    // L = 1: this wave's GGSW column for the next CMUX is loaded into registers right after the
-    // current MAC, so its L2/MALL latency hides behind the inverse FFT, the rotation and the
-    // forward FFT (the vmcnt wait lands at the MAC; no other vector loads in the loop).
-    constexpr bool PREF = PBS_GGSW_PREFETCH && L == 1 && !STAGE;
-    double2 gpre[PREF ? V * (K + 1) : 1];
-    auto prefetch = [&](int ii) {
-        const double2 *g = gcol + (size_t)ii * ggsw_stride;
-#pragma unroll
-        for (int s = 0; s < V; s++)
-#pragma unroll
-            for (int r = 0; r <= K; r++) gpre[s * (K + 1) + r] = g[(size_t)r * (K + 1) * M + s * 64];
-    };
-    if constexpr (PREF) {
-        prefetch(0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
 
     const double k32 = torus_k32();
     for (int i = 0; i < n; i++) {
@@ -245,11 +172,11 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         // mask element through the scalar unit: an s_load waits on lgkmcnt, never on the vmcnt
-        // that the GGSW LDS-DMA occupies
+        // of the GGSW loads
         const uint32_t at = pbs_modulus_switch<LOG2N>(in_s[i]);
         const bool full_odd = (at / N) & 1;
         const int rem = at % N;
-        const double2 *ggsw = STAGE ? s_ggsw + (size_t)wave * M + lane : gcol + (size_t)i * ggsw_stride;
+        const double2 *ggsw = gcol + (size_t)i * ggsw_stride;
 
         // ct1 = X^{a~} ct0 - ct0 (polynomial_algorithms.rs:425-490) through the LDS buffer
         // (wave-private: the other waves' last reads of it ended at the post-MAC barrier)
@@ -281,7 +208,7 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
         };
         auto ct1_hi = [&](int h) -> uint32_t { return rot_finish(h, PBS_TSKIP_ROT ? 0 : rot_gather(h)); };
         uint32_t st[L > 1 ? 2 * V : 1];
-        if constexpr (L == 2 && CLASSIC_DIGIT2) {
+        if constexpr (L == 2) {
             // st[b] = level-L int16 pair of positions (b, V + b), st[V + b] = level L-1 (Digit2)
 #pragma unroll
             for (int b = 0; b < V; b++) digit2.pair(ct1_hi(b), ct1_hi(V + b), st[b], st[V + b]);
@@ -296,12 +223,15 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
 #pragma unroll 1
         for (int lvl = L; lvl >= 1; lvl--) {
             cx v[V];
-            constexpr int RG = (L == 1 && !PBS_TSKIP_ROT) ? (PBS_ROT_GROUP < V ? PBS_ROT_GROUP : V) : 0;
+            // L = 1: slots per group of rotation gathers, and groups in flight ahead of the one
+            // being consumed (measured, DESIGN.md 5.1: one slot, one group ahead; the grouped form
+            // stays general because written out for that one case hipcc emits a different CMUX loop)
+            constexpr int ROT_GROUP = 1, ROT_AHEAD = 1;
+            constexpr int RG = (L == 1 && !PBS_TSKIP_ROT) ? ROT_GROUP : 0;
             if constexpr (RG > 0) {
-                // L = 1: the gathers and twist reads of RG slots are issued PBS_ROT_AHEAD groups
-                // ahead of the digits that consume them, fenced by scheduling barriers (left to
-                // itself the scheduler pairs every gather with its use: 2V serial LDS round trips
-                // per CMUX).  Measured, DESIGN.md 5.1: one slot, one group ahead.
+                // the gathers and twist reads of RG slots are issued ROT_AHEAD groups ahead of
+                // the digits that consume them, fenced by scheduling barriers (left to itself the
+                // scheduler pairs every gather with its use: 2V serial LDS round trips per CMUX)
                 static_assert(V % RG == 0, "group size divides the slots per lane");
                 uint64_t ya[V], yb[V];
                 double2 wt[V];
@@ -313,7 +243,7 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
                         wt[b] = s_twist[lane + 64 * b];
                     }
                 };
-                constexpr int RA = PBS_ROT_AHEAD * RG;
+                constexpr int RA = ROT_AHEAD * RG;
 #pragma unroll
                 for (int b0 = 0; b0 < RA && b0 < V; b0 += RG) issue(b0);
 #pragma unroll
@@ -334,7 +264,7 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
                 if constexpr (L == 1) {
                     d0 = digit_l1(ct1_hi(b));
                     d1 = digit_l1(ct1_hi(V + b));
-                } else if constexpr (L == 2 && CLASSIC_DIGIT2) {
+                } else if constexpr (L == 2) {
                     const uint32_t w = lvl == L ? st[b] : st[V + b];
                     d0 = (int32_t)(int16_t)(w & 0xffffu);
                     d1 = (int32_t)(int16_t)(w >> 16);
@@ -352,17 +282,16 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
 #pragma unroll
             for (int s = 0; s < V; s++)
                 reinterpret_cast<double2 *>(xb)[s * 64 + lane] = make_double2(v[s].re, v[s].im);
-            if constexpr (STAGE) stage_ggsw_wait();  // this wave's part of GGSW_i has landed
             xsync();
             // output column c = wave: sum_r F_r * G[lvl][r][c]   (ggsw.rs:524-567, update_with_fmadd)
             const double2 *lm = ggsw + (size_t)(lvl - 1) * (K + 1) * (K + 1) * M;
 #pragma unroll
             for (int s = 0; s < V; s++) {
-                if (s % PBS_MAC_SB == 0) __builtin_amdgcn_sched_barrier(0);  // bound loads in flight
+                if (s % 4 == 0) __builtin_amdgcn_sched_barrier(0);  // 4 slots per scheduling region: bounds loads in flight
                 cx o = (L > 1 && lvl != L) ? acc[L > 1 ? s : 0] : cx{0.0, 0.0};
 #pragma unroll
                 for (int r = 0; r <= K; r++) {
-                    const double2 gg = PREF ? gpre[PREF ? s * (K + 1) + r : 0] : lm[(size_t)r * (K + 1) * M + s * 64];
+                    const double2 gg = lm[(size_t)r * (K + 1) * M + s * 64];
                     double2 ff;
                     if (Cfg::MAC_LDS) {  // every row from LDS: no wave-dependent branch
                         ff = reinterpret_cast<const double2 *>(xct + r * XL)[s * 64 + lane];
@@ -382,22 +311,13 @@ __global__ void __launch_bounds__((64 * (K + 1) * PbsConfig<N, K, L>::CPW), (Pbs
                 if constexpr (L > 1) acc[s] = o;
                 else v[s] = o;
             }
-            xsync();  // every wave is done reading the published spectra (and the staged GGSW)
-            if constexpr (PREF) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (i + 1 < n) prefetch(i + 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if constexpr (STAGE) {
-                // prefetch GGSW_{i+1} into LDS: overlaps the inverse FFT, the rotation and the
-                // forward FFT; the next publish barrier (its vmcnt(0)) retires it
-                if (lvl == 1 && i + 1 < n) stage_ggsw(i + 1);
-            }
+            xsync();  // every wave is done reading the published spectra
             if constexpr (L == 1) {
                 Fft::inverse(v, xb, tw, lane, wsync);
 #pragma unroll
                 for (int b = 0; b < V; b++) {
-                    if (b % PBS_BWD_SB == 0) __builtin_amdgcn_sched_barrier(0);
+                    // 2 slots per scheduling region: bounds the live f64 temporaries
+                    if (b % 2 == 0) __builtin_amdgcn_sched_barrier(0);
                     const double2 w = s_twist[lane + 64 * b];  // the resident key carries the 1/M
                     backward_sub(v[b], cx{w.x, w.y}, n0[b], n0[V + b], k32);
                 }

@@ -2,42 +2,6 @@
 #pragma once
 #include "fft_device.h"
 
-#ifndef PBS_WAVE_LOCAL
-#define PBS_WAVE_LOCAL 1
-#endif
-#ifndef PBS_BWD_SB
-#define PBS_BWD_SB 2  // backward-conversion slots per scheduling region (bounds live f64 temporaries)
-#endif
-#ifndef PBS_MAC_SB
-#define PBS_MAC_SB 4  // MAC slots per scheduling region
-#endif
-#ifndef PBS_GGSW_PREFETCH
-#define PBS_GGSW_PREFETCH 0  // L = 1: GGSW_{i+1} column into registers during CMUX i's inverse FFT (measured 8% slower: AGPR shuffles)
-#endif
-#ifndef PBS_MAC_FROM_LDS
-#define PBS_MAC_FROM_LDS -1  // classic kernel: -1 per-shape default (PbsConfig::MAC_LDS), 0/1 force
-#endif
-#ifndef PBS_WAVES_PER_EU
-#define PBS_WAVES_PER_EU 0  // 0: per-shape default (PbsConfig::WPE); the multi-bit kernel uses 1
-#endif
-
-#ifndef PBS_SYNC_SLEEP
-#define PBS_SYNC_SLEEP 1  // s_sleep argument between polls of a partner's flag (64 clocks per unit)
-#endif
-#define PBS_STR2(x) #x
-#define PBS_STR(x) PBS_STR2(x)
-#define PBS_SYNC_SLEEP_STR PBS_STR(PBS_SYNC_SLEEP)
-#ifndef PBS_GROUP_SYNC
-#define PBS_GROUP_SYNC 1  // CMUX-loop syncs between the (k+1) waves of ONE ciphertext (LDS flags), not s_barrier
-#endif
-
-#ifndef PBS_SLOT_MAJOR
-#define PBS_SLOT_MAJOR 0  // classic kernel: 1 = wave w serves (row w / CPW, ciphertext w % CPW) -- one ciphertext per SIMD
-#endif
-#ifndef PBS_PERSIST
-#define PBS_PERSIST -1  // classic PBS persistent grid + ticket queue: -1 per-shape default (PbsConfig), 0/1 force
-#endif
-
 namespace tfhe_mi355 {
 
 // Workgroups of a kernel resident at once on the current device (CUs x occupancy); the
@@ -113,7 +77,7 @@ struct GroupSync {
                 "s_nop 1\n\t"
                 "s_cmp_lt_u32 %[s], %[q]\n\t"
                 "s_cbranch_scc0 2f\n\t"
-                "s_sleep " PBS_SYNC_SLEEP_STR "\n\t"
+                "s_sleep 1\n\t"  // 64 clocks between polls of a partner's flag
                 "s_branch 1b\n\t"
                 "2:"
                 : [v] "=&v"(tmp), [s] "=&s"(stmp)
@@ -202,12 +166,6 @@ struct Digit2 {
 #ifndef PBS_MB_TSKIP_MONO
 #define PBS_MB_TSKIP_MONO 0
 #endif
-#ifndef PBS_MB_SWK
-#define PBS_MB_SWK 4   // twist-table swizzle: position r ^ ((r >> SWK) & SWM) (M = 1024)
-#endif
-#ifndef PBS_MB_SWM
-#define PBS_MB_SWM 23
-#endif
 // Twist table in LDS, shared by the linear twist reads (digits, backward conversion) and the
 // keybundle's monomial reads.  A monomial read fetches entry r of t = d (1 - 4 f) mod 2N, lanes
 // 16 apart in f stepping t by 4d and the two 16-lane halves of a ds_read_b64 group by 256d.  As one
@@ -224,23 +182,17 @@ struct Digit2 {
 // case of the shift-mask family for that kernel's read pattern (lanes step t by 16 d R): 2.12
 // distinct entries per bank on average, worst 4, against 19.6 / 32 for the plain planes
 // (scripts/probes/twist_swizzle_search_8192.py; k = 7 gives 2.10 but worst 6).)
-#ifndef PBS_MB8_SWK
-#define PBS_MB8_SWK 6
-#endif
-#ifndef PBS_MB8_SWM
-#define PBS_MB8_SWM 31
-#endif
 template <int M>
 struct TwistSwz {
     static constexpr uint32_t K = 0, MASK = 0;
 };
 template <>
 struct TwistSwz<1024> {
-    static constexpr uint32_t K = PBS_MB_SWK, MASK = PBS_MB_SWM;
+    static constexpr uint32_t K = 4, MASK = 23;
 };
 template <>
 struct TwistSwz<4096> {
-    static constexpr uint32_t K = PBS_MB8_SWK, MASK = PBS_MB8_SWM;
+    static constexpr uint32_t K = 6, MASK = 31;
 };
 template <int M>
 struct TwistLds {

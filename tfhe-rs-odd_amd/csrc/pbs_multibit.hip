@@ -25,28 +25,18 @@ namespace tfhe_mi355 {
 
 // Ciphertexts per workgroup and register budget.  As the classic 2_2 kernel: 4 ciphertexts per
 // workgroup at 2 waves/SIMD (31 KiB of tables + 8 x 16 KiB exchange buffers = 159 KiB of LDS),
-// the MAC reading every row spectrum from LDS and a one-slot issue window for the GGSW loads so
-// the wave fits 256 registers.
-#ifndef PBS_MB_CPW
-#define PBS_MB_CPW 4
-#endif
-#ifndef PBS_MB_WINDOW
-#define PBS_MB_WINDOW 4  // MAC slots whose GGSW loads may be in flight (4: 234 VGPRs at g = 3; 8 spills)
-#endif
-#ifndef PBS_MB_MAC_LDS
-#define PBS_MB_MAC_LDS 1
-#endif
-#ifndef PBS_MB_BUFLD
-#define PBS_MB_BUFLD 1  // GGSW loads through a buffer resource: scalar offsets, no 64-bit VALU address adds
-#endif
+// the MAC reading every row spectrum from LDS and a bounded issue window for the GGSW loads so
+// the wave fits 256 registers.  The GGSW loads go through a buffer resource: scalar offsets, no
+// 64-bit VALU address adds.
+constexpr int MB_CPW = 4;
+constexpr int MB_WPE = 2;     // waves per SIMD
+constexpr int MB_WINDOW = 4;  // MAC slots whose GGSW loads may be in flight (4: 234 VGPRs at g = 3; 8 spills)
 // TwistLds (the twist table in LDS, shared with the multi-bit latency kernel): pbs_common.h
 
-constexpr int mb_wpe() { return PBS_WAVES_PER_EU > 0 ? PBS_WAVES_PER_EU : (PBS_MB_CPW >= 4 ? 2 : 1); }
-
 template <int N, int K, int L, int G>
-__global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
+__global__ void __launch_bounds__(64 * (K + 1) * MB_CPW, MB_WPE)
     pbs_multibit_kernel(MultiBitPbsLaunch a) {
-    constexpr int CPW = PBS_MB_CPW;
+    constexpr int CPW = MB_CPW;
     constexpr int M = N / 2;
     constexpr int V = M / 64;
     constexpr int LOG2N = ilog2(N);
@@ -78,9 +68,8 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
     Tw::fill(reinterpret_cast<double *>(lds + Lay::twist_off), a.twist, threadIdx.x, blockDim.x);
     // spectrum exchange among this ciphertext's waves (GroupSync, pbs_common.h): flags after the buffers
     uint32_t *gflags = reinterpret_cast<uint32_t *>(smem + Lay::bytes((K + 1) * CPW));
-    if (PBS_GROUP_SYNC && threadIdx.x < (K + 1) * CPW) gflags[threadIdx.x] = 0;
-    std::conditional_t<(bool)PBS_GROUP_SYNC, GroupSync<K + 1>, BlockSync> xsync;
-    if constexpr ((bool)PBS_GROUP_SYNC) xsync = {lds_addr(gflags + slot * (K + 1)), lds_addr(gflags + wid)};
+    if (threadIdx.x < (K + 1) * CPW) gflags[threadIdx.x] = 0;
+    GroupSync<K + 1> xsync{lds_addr(gflags + slot * (K + 1)), lds_addr(gflags + wid)};
     Fft::Lds::template fill<M>(lds + Lay::s1_off, lds + Lay::s2_off, a.W, threadIdx.x, blockDim.x);
     const typename Fft::Lds tw{lds + Lay::s1_off, lds + Lay::s2_off};
     sync();
@@ -108,8 +97,7 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
 
     constexpr size_t ggsw_len = (size_t)L * (K + 1) * (K + 1) * M;
     constexpr size_t lvl_len = (size_t)(K + 1) * (K + 1) * M;
-    const double2 *gcol = a.fbsk + (size_t)wave * M + lane;  // column c = wave, this lane
-    // the same column as a buffer resource: per-lane byte offset (VGPR, loop invariant; laundered
+    // column c = wave as a buffer resource: per-lane byte offset (VGPR, loop invariant; laundered
     // through the issue window) + scalar offsets for group / selector / level / row / slot
     const __amdgpu_buffer_rsrc_t gres = make_rsrc(a.fbsk + (size_t)wave * M);
     const int groups = n / G;
@@ -145,7 +133,6 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
             tb[sel] = d4[sel] - 4u * d4[sel] * fl;  // t mod 2^32 at freq_slot 0
             d4[sel] *= 4u;
         }
-        const double2 *grp = gcol + (size_t)j * NSEL * ggsw_len;
         const uint32_t gsoff = (uint32_t)((size_t)j * NSEL * ggsw_len * 16);  // < 2^31 (MB-BSK bytes)
 
         uint32_t st[L > 1 ? 2 * V : 1];
@@ -178,18 +165,17 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
             for (int s = 0; s < V; s++)
                 reinterpret_cast<double2 *>(xb)[s * 64 + lane] = make_double2(v[s].re, v[s].im);
             xsync();
-            const double2 *lm = grp + (size_t)(lvl - 1) * lvl_len;
             const uint32_t lsoff = gsoff + (uint32_t)((lvl - 1) * lvl_len * 16);
             uint32_t loff = 16u * (uint32_t)lane;
 #pragma unroll
             for (int s = 0; s < V; s++) {
                 // Issue window: slot s's GGSW loads and monomial reads take their addresses from
-                // an opaque copy that depends on the result of slot s-2, so at most two slots of
-                // operands are in flight (hoisted all at once they need ~1 KiB/lane and spill).
-                if (s >= PBS_MB_WINDOW) {
-                    const double dep = (L > 1) ? acc[L > 1 ? s - PBS_MB_WINDOW : 0].re : v[s - PBS_MB_WINDOW].re;
-                    if (PBS_MB_BUFLD) asm volatile("" : "+v"(loff) : "v"(dep));
-                    else asm volatile("" : "+v"(lm) : "v"(dep));
+                // an opaque copy that depends on the result of slot s - MB_WINDOW, so at most
+                // MB_WINDOW slots of operands are in flight (hoisted all at once they need
+                // ~1 KiB/lane and spill).
+                if (s >= MB_WINDOW) {
+                    const double dep = (L > 1) ? acc[L > 1 ? s - MB_WINDOW : 0].re : v[s - MB_WINDOW].re;
+                    asm volatile("" : "+v"(loff) : "v"(dep));
 #pragma unroll
                     for (int sel = 1; sel < NSEL; sel++) asm volatile("" : "+v"(tb[sel]) : "v"(dep));
                 }
@@ -201,24 +187,16 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
 #pragma unroll
                 for (int r = 0; r <= K; r++) {
                     // KB[lvl][r][c] at this frequency (keybundle, oracle mb_keybundle order)
-                    const double2 *gp = lm + (size_t)r * (K + 1) * M + s * 64;
                     const uint32_t rsoff = lsoff + (uint32_t)((r * (K + 1) * M + s * 64) * 16);
-                    double2 kb = PBS_MB_BUFLD ? buffer_ld_d2(gres, loff, rsoff) : gp[0];
+                    double2 kb = buffer_ld_d2(gres, loff, rsoff);
 #pragma unroll
                     for (int sel = 1; sel < NSEL; sel++) {
-                        const double2 gg = PBS_MB_BUFLD ? buffer_ld_d2(gres, loff, rsoff + (uint32_t)(sel * ggsw_len * 16))
-                                                        : gp[(size_t)sel * ggsw_len];
+                        const double2 gg = buffer_ld_d2(gres, loff, rsoff + (uint32_t)(sel * ggsw_len * 16));
                         kb.x = fma(gg.x, mono[sel].re, fma(-gg.y, mono[sel].im, kb.x));
                         kb.y = fma(gg.x, mono[sel].im, fma(gg.y, mono[sel].re, kb.y));
                     }
-                    double2 ff;
-                    if (PBS_MB_MAC_LDS) {  // every row from LDS: no wave-dependent branch
-                        ff = reinterpret_cast<const double2 *>(xct + r * XL)[s * 64 + lane];
-                    } else if (r == wave) {
-                        ff = make_double2(v[s].re, v[s].im);
-                    } else {
-                        ff = reinterpret_cast<const double2 *>(xct + r * XL)[s * 64 + lane];
-                    }
+                    // every row from LDS, the wave's own included: no wave-dependent branch
+                    const double2 ff = reinterpret_cast<const double2 *>(xct + r * XL)[s * 64 + lane];
                     if (lvl == L && r == 0) {
                         o.re = fma(kb.x, ff.x, -(kb.y * ff.y));
                         o.im = fma(kb.x, ff.y, kb.y * ff.x);
@@ -266,11 +244,7 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
     }
 }
 
-#ifndef PBS_MB_SHARED
-#define PBS_MB_SHARED 1  // slot-split MAC phase: each GGSW element is loaded once per workgroup
-#endif
-
-// Slot-split variant (PBS_MB_SHARED, L = 1).  The kernel above streams every GGSW column once per
+// Slot-split variant (L = 1): each GGSW element is loaded once per workgroup.  The kernel above streams every GGSW column once per
 // ciphertext: 2^g (k+1)^2 M 16 B = 512 KiB per group and ciphertext at g = 3 (155 MB per PBS) from
 // L2/MALL -- ~20 TB/s of L2->CU traffic at 128k PBS/s, and its waves wait on it (PMC: s_waitcnt
 // 0.48 of wave cycles, VALU 0.26).  Here the CPW ciphertexts of a workgroup share each load:
@@ -284,10 +258,10 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
 // order are those of the kernel above (keybundle in selector order, MAC over rows in order), so
 // the outputs are bit-identical; a ciphertext's GGSW traffic drops by CPW (4x).
 template <int N, int K, int L, int G>
-__global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
+__global__ void __launch_bounds__(64 * (K + 1) * MB_CPW, MB_WPE)
     pbs_multibit_shared_kernel(MultiBitPbsLaunch a) {
     static_assert(L == 1, "slot-split kernel: one decomposition level (every multi-bit set)");
-    constexpr int CPW = PBS_MB_CPW;
+    constexpr int CPW = MB_CPW;
     constexpr int W = (K + 1) * CPW;  // waves per workgroup
     constexpr int M = N / 2;
     constexpr int V = M / 64;
@@ -503,15 +477,15 @@ __global__ void __launch_bounds__(64 * (K + 1) * PBS_MB_CPW, mb_wpe())
 template <int N, int K, int L, int G>
 static hipError_t launch_mb_t(const MultiBitPbsLaunch &a, hipStream_t s) {
     constexpr int M = N / 2;
-    constexpr size_t lds = PbsLds<M>::bytes((K + 1) * PBS_MB_CPW) + (PBS_GROUP_SYNC ? 4 * (K + 1) * PBS_MB_CPW : 0);
+    constexpr size_t lds = PbsLds<M>::bytes((K + 1) * MB_CPW) + 4 * (K + 1) * MB_CPW;  // buffers + GroupSync flags
     static_assert(lds <= 160 * 1024, "LDS per workgroup exceeds a CU");
     if (a.count == 0) return hipSuccess;
     if (a.n % G) return hipErrorInvalidValue;
-    const int blocks = (a.count + PBS_MB_CPW - 1) / PBS_MB_CPW;
-    if constexpr (PBS_MB_SHARED && L == 1 && (K + 1) * (K + 1) * (1 << G) <= 32)
-        hipLaunchKernelGGL((pbs_multibit_shared_kernel<N, K, L, G>), dim3(blocks), dim3(64 * (K + 1) * PBS_MB_CPW), lds, s, a);
+    const int blocks = (a.count + MB_CPW - 1) / MB_CPW;
+    if constexpr (L == 1 && (K + 1) * (K + 1) * (1 << G) <= 32)
+        hipLaunchKernelGGL((pbs_multibit_shared_kernel<N, K, L, G>), dim3(blocks), dim3(64 * (K + 1) * MB_CPW), lds, s, a);
     else
-        hipLaunchKernelGGL((pbs_multibit_kernel<N, K, L, G>), dim3(blocks), dim3(64 * (K + 1) * PBS_MB_CPW), lds, s, a);
+        hipLaunchKernelGGL((pbs_multibit_kernel<N, K, L, G>), dim3(blocks), dim3(64 * (K + 1) * MB_CPW), lds, s, a);
     return hipGetLastError();
 }
 
