@@ -353,6 +353,61 @@ int tfhe_mi355_glwe_poly_mul_async(TfheMi355Context *ctx, const uint64_t *d_glwe
                                    const uint64_t *d_polys, size_t npoly, size_t count, int extract,
                                    uint64_t *d_out, void *stream);
 
+/* GGSW x GLWE operations on GGSW ciphertexts that are data, not the context's key: every item of a
+ * batch brings its own, and the decomposition (base_log, level; base_log * level <= 32) is an
+ * argument of the call -- the circuit-bootstrap decomposition of WoP-PBS, not the PBS one.  N in
+ * {256, 512, 1024, 2048}, 1 <= k <= 5 (the context's); anything else fails.
+ * A GGSW in the standard domain is laid out as one bootstrap-key element, [level 1..L][row k+1]
+ * [(k+1)N] u64 with level l at index l-1.  The host-pointer forms take the list in the standard
+ * domain and convert it on the device; the _async forms take the Fourier list (engine layout,
+ * tfhe_mi355_ggsw_list_fourier_bytes bytes) that tfhe_mi355_ggsw_list_convert_async produces, the
+ * device-side convert_standard_ggsw_ciphertext_to_fourier (ggsw_conversion.rs:18-64).
+ * ggsw_indexes [count] picks the GGSW of each item (NULL: item i uses GGSW i; ggsw_count >= count).
+ *
+ * tfhe_mi355_ggsw_external_product: glwe_inout[i] += ggsw[i] (x) glwe_in[i], both [count][(k+1)N].
+ * Replaces add_external_product_assign (algorithms/lwe_programmable_bootstrapping.rs:309-473;
+ * fft_impl/fft64/crypto/ggsw.rs:477-598).
+ * tfhe_mi355_ggsw_cmux: out[i] = ct0[i] + ggsw[i] (x) (ct1[i] - ct0[i]); out == ct0 is allowed, ct1 is
+ * left untouched.  Replaces cmux_assign (lwe_programmable_bootstrapping.rs:552-763;
+ * fft_impl/fft64/crypto/ggsw.rs:766-777), whose result lands in ct0. */
+int tfhe_mi355_ggsw_external_product(TfheMi355Context *ctx, const uint64_t *ggsw_list, size_t ggsw_count,
+                                     uint32_t base_log, uint32_t level, const uint32_t *ggsw_indexes,
+                                     const uint64_t *glwe_in, uint64_t *glwe_inout, size_t count);
+int tfhe_mi355_ggsw_external_product_async(TfheMi355Context *ctx, const void *d_fourier_ggsw, size_t ggsw_count,
+                                           uint32_t base_log, uint32_t level, const uint32_t *d_ggsw_indexes,
+                                           const uint64_t *d_glwe_in, uint64_t *d_glwe_inout, size_t count,
+                                           void *stream);
+int tfhe_mi355_ggsw_cmux(TfheMi355Context *ctx, const uint64_t *ggsw_list, size_t ggsw_count, uint32_t base_log,
+                         uint32_t level, const uint32_t *ggsw_indexes, const uint64_t *ct0, const uint64_t *ct1,
+                         uint64_t *out, size_t count);
+int tfhe_mi355_ggsw_cmux_async(TfheMi355Context *ctx, const void *d_fourier_ggsw, size_t ggsw_count,
+                               uint32_t base_log, uint32_t level, const uint32_t *d_ggsw_indexes,
+                               const uint64_t *d_ct0, const uint64_t *d_ct1, uint64_t *d_out, size_t count,
+                               void *stream);
+int tfhe_mi355_ggsw_list_fourier_bytes(TfheMi355Context *ctx, size_t ggsw_count, uint32_t level, size_t *bytes);
+int tfhe_mi355_ggsw_list_convert_async(TfheMi355Context *ctx, const uint64_t *d_ggsw_list, size_t ggsw_count,
+                                       uint32_t level, void *d_fourier_ggsw, void *stream);
+
+/* Vertical packing, the leveled half of WoP-PBS: evaluates a LUT of npoly * N entries at the index
+ * whose bits are GGSW-encrypted, most significant first.  ggsw_list [count][nbits] GGSWs, luts
+ * [lut_count][npoly][N] with lut_indexes [count] as the PBS takes them (NULL: LUT 0), lwe_out
+ * [count][k*N+1].  The first log2(npoly) GGSWs drive a CMUX tree over the LUT polynomials, the
+ * others a blind rotation by monomial degrees 1, 2, 4, ... (last GGSW first), then the degree-0
+ * sample is extracted.  Replaces vertical_packing (fft_impl/fft64/crypto/wop_pbs/mod.rs:785-853:
+ * cmux_tree_memory_optimized :468-592, blind_rotate_assign :866-892).  Fails when npoly is not a
+ * power of two, when log2(npoly) > nbits (the reference then skips the tree and reads one
+ * polynomial only), when nbits - log2(npoly) > log2(N), or when nbits = 0.
+ * The _async form takes the Fourier GGSW list and tfhe_mi355_vertical_packing_scratch bytes of device
+ * scratch (the tree's ping-pong accumulators); a NULL or short scratch fails. */
+int tfhe_mi355_vertical_packing(TfheMi355Context *ctx, const uint64_t *ggsw_list, uint32_t base_log, uint32_t level,
+                                uint32_t nbits, const uint64_t *luts, size_t lut_count, size_t npoly,
+                                const uint32_t *lut_indexes, size_t count, uint64_t *lwe_out);
+int tfhe_mi355_vertical_packing_async(TfheMi355Context *ctx, const void *d_fourier_ggsw, uint32_t base_log,
+                                      uint32_t level, uint32_t nbits, const uint64_t *d_luts, size_t lut_count,
+                                      size_t npoly, const uint32_t *d_lut_indexes, size_t count, uint64_t *d_lwe_out,
+                                      void *d_scratch, size_t scratch_bytes, void *stream);
+int tfhe_mi355_vertical_packing_scratch(TfheMi355Context *ctx, size_t npoly, size_t count, size_t *bytes);
+
 /* Batched LWE keyswitch (big key -> small key): lwe_in count x (k*N+1) -> lwe_out count x (n+1).
  * Replaces keyswitch_lwe_ciphertext (lwe_keyswitch.rs:96-170). */
 int tfhe_mi355_keyswitch(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *lwe_out, size_t count);

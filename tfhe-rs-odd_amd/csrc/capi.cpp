@@ -740,6 +740,153 @@ void launch_glwe_poly_mul_dev(TfheMi355Context *c, const uint64_t *d_glwe, size_
     check(launch_glwe_poly_mul(a, s), "launch glwe poly mul");
 }
 
+// ---- GGSW operations (ggsw_ops.hip): per-item GGSW ciphertexts, decomposition chosen per call ----
+size_t ggsw_polys(const TfheMi355Context *c, uint32_t level) { return (size_t)level * (c->k() + 1) * (c->k() + 1); }
+size_t ggsw_std_words(const TfheMi355Context *c, uint32_t level) { return ggsw_polys(c, level) * c->N(); }
+size_t ggsw_fourier_bytes(const TfheMi355Context *c, uint32_t level) {
+    return ggsw_polys(c, level) * (c->N() / 2) * sizeof(double2);
+}
+
+void require_ggsw_shape(const TfheMi355Context *c, uint32_t base_log, uint32_t level) {
+    if (!ggsw_ops_supported((int)c->N(), (int)c->k()))
+        fail("GGSW operations support N in {256, 512, 1024, 2048} and 1 <= k <= 5, not N = %zu, k = %zu", c->N(), c->k());
+    if (base_log == 0 || level == 0 || base_log > 32 || level > 32 || base_log * level > 32)
+        fail("GGSW decomposition base_log %u x level %u outside the 32-bit decomposer (base_log * level <= 32)",
+             base_log, level);
+}
+
+void validate_ggsw_indexes(const uint32_t *idx, size_t count, size_t ggsw_count) {
+    if (!idx) {
+        if (ggsw_count < count) fail("GGSW list has %zu ciphertexts for %zu items (no ggsw_indexes)", ggsw_count, count);
+        return;
+    }
+    for (size_t i = 0; i < count; i++)
+        if (idx[i] >= ggsw_count) fail("ggsw_indexes[%zu] = %u out of range (ggsw_count %zu)", i, idx[i], ggsw_count);
+}
+
+void ggsw_list_to_fourier_dev(TfheMi355Context *c, const uint64_t *d_std, double2 *d_fourier, size_t ggsw_count,
+                              uint32_t level, hipStream_t s) {
+    TimedLaunch tl(c->timer_or_null(), "ggsw_to_fourier", s);
+    check(launch_bsk_to_fourier((int)c->N(), d_std, d_fourier, ggsw_count * ggsw_polys(c, level), c->tables, s),
+          "launch GGSW list conversion");
+}
+
+GgswCmuxLaunch ggsw_launch_args(TfheMi355Context *c, const double2 *d_fggsw, size_t ggsw_blocks, const uint32_t *d_idx,
+                                uint32_t base_log, uint32_t level) {
+    GgswCmuxLaunch a{};
+    a.fggsw = d_fggsw;
+    a.ggsw_indexes = d_idx;
+    a.ggsw_blocks = ggsw_blocks;
+    a.ggsw_per_item = 1;
+    a.nodes_per_item = 1;
+    a.in_stride = c->glwe_len();
+    a.base_log = (int)base_log;
+    a.level = (int)level;
+    a.W = c->tables.W;
+    a.twist = c->tables.twist;
+    return a;
+}
+
+// external product (mode GGSW_EP: in1 = glwe_in, out accumulated) or CMUX (GGSW_CMUX) of `count` items
+void launch_ggsw_node_dev(TfheMi355Context *c, int mode, const double2 *d_fggsw, size_t ggsw_count,
+                          const uint32_t *d_idx, uint32_t base_log, uint32_t level, const uint64_t *d_in0,
+                          const uint64_t *d_in1, uint64_t *d_out, size_t count, hipStream_t s) {
+    require_ggsw_shape(c, base_log, level);
+    if (count == 0) return;
+    if (ggsw_count == 0) fail("empty GGSW list");
+    if (!d_idx && ggsw_count < count) fail("GGSW list has %zu ciphertexts for %zu items (no ggsw_indexes)", ggsw_count, count);
+    GgswCmuxLaunch a = ggsw_launch_args(c, d_fggsw, ggsw_count, d_idx, base_log, level);
+    a.mode = mode;
+    a.in0 = d_in0;
+    a.in1 = d_in1;
+    a.out = d_out;
+    a.nodes = count;
+    TimedLaunch tl(c->timer_or_null(), mode == GGSW_EP ? "ggsw_external_product" : "ggsw_cmux", s);
+    check(launch_ggsw_cmux((int)c->N(), (int)c->k(), a, s), "launch GGSW node");
+}
+
+// vertical packing: log2(npoly) tree bits, then nbits - log2(npoly) rotation bits
+struct VpShape {
+    uint32_t nt, nr;
+};
+VpShape vp_shape(const TfheMi355Context *c, uint32_t nbits, size_t npoly) {
+    if (npoly == 0 || npoly > 0x40000000u || !is_pow2((uint32_t)npoly))
+        fail("vertical packing: the LUT has %zu polynomials, not a power of two", npoly);
+    uint32_t nt = 0;
+    while (((size_t)1 << nt) < npoly) nt++;
+    if (nbits == 0) fail("vertical packing: no GGSW ciphertext");
+    if (nt > nbits) fail("vertical packing: %zu LUT polynomials need %u tree bits, only %u GGSWs given", npoly, nt, nbits);
+    uint32_t log2n = 0;
+    while (((size_t)1 << log2n) < c->N()) log2n++;
+    if (nbits - nt > log2n)
+        fail("vertical packing: %u rotation bits exceed log2(N) = %u", nbits - nt, log2n);
+    return {nt, nbits - nt};
+}
+
+// two ping-pong GLWE buffers: the tree's first level leaves npoly/2 nodes per item, the next npoly/4
+size_t vp_scratch_bytes(const TfheMi355Context *c, size_t npoly, size_t count) {
+    const size_t a = std::max<size_t>(npoly / 2, 1), b = std::max<size_t>(npoly / 4, 1);
+    return align256(count * a * c->glwe_len() * 8) + align256(count * b * c->glwe_len() * 8);
+}
+
+void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, uint32_t base_log, uint32_t level,
+                                 uint32_t nbits, const uint64_t *d_luts, size_t lut_count, size_t npoly,
+                                 const uint32_t *d_lut_idx, size_t count, uint64_t *d_lwe_out, void *scratch,
+                                 size_t scratch_bytes, hipStream_t s) {
+    require_ggsw_shape(c, base_log, level);
+    const VpShape sh = vp_shape(c, nbits, npoly);
+    if (lut_count == 0 || lut_count > 0xffffffffu) fail("lut_count out of range");
+    if (count == 0) return;
+    if (count * std::max<size_t>(npoly / 2, 1) > 0x7fffffffu) fail("count too large");
+    require_scratch(scratch ? scratch_bytes : 0, vp_scratch_bytes(c, npoly, count));
+    const size_t glwe = c->glwe_len();
+    uint64_t *buf[2] = {reinterpret_cast<uint64_t *>(scratch),
+                        reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(scratch) +
+                                                     align256(count * std::max<size_t>(npoly / 2, 1) * glwe * 8))};
+    GgswCmuxLaunch a = ggsw_launch_args(c, d_fggsw, count, nullptr, base_log, level);
+    a.ggsw_per_item = (int)nbits;
+    a.lut_indexes = d_lut_idx;
+    a.lut_count = (uint32_t)lut_count;
+    a.npoly = (int)npoly;
+    const uint64_t *cur = nullptr;  // the accumulators so far (null: still the LUT itself)
+    // CMUX tree, level by level: layer j pairs the nodes (2i, 2i+1) of the layer before under GGSW
+    // nt-1-j (the list is most significant bit first; cmux_tree_memory_optimized walks it reversed)
+    for (uint32_t j = 0; j < sh.nt; j++) {
+        const bool last = j + 1 == sh.nt && sh.nr == 0;
+        a.mode = GGSW_CMUX;
+        a.leaf = cur == nullptr;
+        a.ggsw_sel = (int)(sh.nt - 1 - j);
+        a.nodes_per_item = npoly >> (j + 1);
+        a.nodes = count * a.nodes_per_item;
+        a.in0 = cur ? cur : d_luts;
+        a.in1 = cur ? cur + glwe : nullptr;
+        a.in_stride = 2 * glwe;
+        a.extract = last;
+        a.out = last ? d_lwe_out : buf[j & 1];
+        TimedLaunch tl(c->timer_or_null(), "ggsw_cmux_tree", s);
+        check(launch_ggsw_cmux((int)c->N(), (int)c->k(), a, s), "launch CMUX tree level");
+        cur = a.out;
+    }
+    // blind rotation by the remaining GGSWs, last first, monomial degrees 1, 2, 4, ... (in place)
+    for (uint32_t i = 0; i < sh.nr; i++) {
+        const bool last = i + 1 == sh.nr;
+        a.mode = GGSW_ROT;
+        a.leaf = cur == nullptr;
+        a.ggsw_sel = (int)(nbits - 1 - i);
+        a.rot = 1 << i;
+        a.nodes_per_item = 1;
+        a.nodes = count;
+        a.in0 = cur ? cur : d_luts;
+        a.in1 = nullptr;
+        a.in_stride = glwe;
+        a.extract = last;
+        a.out = last ? d_lwe_out : (cur ? const_cast<uint64_t *>(cur) : buf[0]);
+        TimedLaunch tl(c->timer_or_null(), "ggsw_rotate", s);
+        check(launch_ggsw_cmux((int)c->N(), (int)c->k(), a, s), "launch rotation step");
+        cur = a.out;
+    }
+}
+
 void validate_lut_indexes(const uint32_t *idx, size_t count, size_t lut_count) {
     if (!idx) return;
     for (size_t i = 0; i < count; i++)
@@ -2355,6 +2502,211 @@ int tfhe_mi355_glwe_poly_mul_async(TfheMi355Context *ctx, const uint64_t *d_glwe
         if (count == 0 || npoly == 0) return;
         launch_glwe_poly_mul_dev(ctx, d_glwe_in, glwe_per_item, d_polys, npoly, count, extract != 0, d_out,
                                  (hipStream_t)stream);
+    });
+}
+
+// ---- GGSW external product, CMUX, vertical packing ---------------------------------------------
+namespace {
+// host form of the external product (ct0 == nullptr: glwe_inout accumulated) and of the CMUX
+void ggsw_node_host(TfheMi355Context *ctx, int mode, const uint64_t *ggsw_list, size_t ggsw_count, uint32_t base_log,
+                    uint32_t level, const uint32_t *ggsw_indexes, const uint64_t *in0, const uint64_t *in1,
+                    uint64_t *out, size_t count) {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    check(hipSetDevice(ctx->device), "hipSetDevice");
+    require_ggsw_shape(ctx, base_log, level);
+    if (count == 0) return;
+    validate_ggsw_indexes(ggsw_indexes, count, ggsw_count);
+    const size_t used = ggsw_indexes ? ggsw_count : count;  // without indexes item i reads GGSW i
+    const size_t std_b = used * ggsw_std_words(ctx, level) * 8, f_b = used * ggsw_fourier_bytes(ctx, level);
+    const size_t rows_b = count * ctx->glwe_len() * 8;
+    DeviceBuffer d_std, d_f, d_a, d_b, d_idx;
+    d_std.reserve(std_b);
+    d_f.reserve(f_b);
+    d_a.reserve(rows_b);
+    d_b.reserve(rows_b);
+    hipStream_t s = ctx->stream;
+    check(hipMemcpyAsync(d_std.ptr, ggsw_list, std_b, hipMemcpyHostToDevice, s), "H2D GGSW list");
+    if (ggsw_indexes) {
+        d_idx.reserve(count * 4);
+        check(hipMemcpyAsync(d_idx.ptr, ggsw_indexes, count * 4, hipMemcpyHostToDevice, s), "H2D GGSW indexes");
+    }
+    // d_a: ct0, or the accumulated glwe_inout; d_b: ct1, or glwe_in
+    check(hipMemcpyAsync(d_a.ptr, mode == GGSW_EP ? out : in0, rows_b, hipMemcpyHostToDevice, s), "H2D glwe");
+    check(hipMemcpyAsync(d_b.ptr, in1, rows_b, hipMemcpyHostToDevice, s), "H2D glwe");
+    ggsw_list_to_fourier_dev(ctx, (const uint64_t *)d_std.ptr, (double2 *)d_f.ptr, used, level, s);
+    launch_ggsw_node_dev(ctx, mode, (const double2 *)d_f.ptr, used, (const uint32_t *)d_idx.ptr, base_log, level,
+                         mode == GGSW_EP ? nullptr : (const uint64_t *)d_a.ptr, (const uint64_t *)d_b.ptr,
+                         (uint64_t *)d_a.ptr, count, s);
+    check(hipMemcpyAsync(out, d_a.ptr, rows_b, hipMemcpyDeviceToHost, s), "D2H glwe");
+    check(hipStreamSynchronize(s), "GGSW node sync");
+}
+
+// a multi-device context's share [a, a + n) of a GGSW list: the whole list when indexed
+const uint64_t *ggsw_share(const TfheMi355Context *c, const uint64_t *list, const uint32_t *idx, uint32_t level,
+                           size_t a) {
+    return idx ? list : list + a * ggsw_std_words(c, level);
+}
+}  // namespace
+
+int tfhe_mi355_ggsw_external_product(TfheMi355Context *ctx, const uint64_t *ggsw_list, size_t ggsw_count,
+                                     uint32_t base_log, uint32_t level, const uint32_t *ggsw_indexes,
+                                     const uint64_t *glwe_in, uint64_t *glwe_inout, size_t count) {
+    return guarded([&] {
+        if (!ctx || (!ggsw_list && count) || (!glwe_in && count) || (!glwe_inout && count)) fail("null argument");
+        if (ctx->multi()) {
+            require_ggsw_shape(ctx, base_log, level);
+            validate_ggsw_indexes(ggsw_indexes, count, ggsw_count);
+            return split_rows(ctx, count, [&](TfheMi355Context *s, size_t a, size_t n) {
+                return tfhe_mi355_ggsw_external_product(
+                    s, ggsw_share(ctx, ggsw_list, ggsw_indexes, level, a), ggsw_indexes ? ggsw_count : n, base_log,
+                    level, ggsw_indexes ? ggsw_indexes + a : nullptr, glwe_in + a * ctx->glwe_len(),
+                    glwe_inout + a * ctx->glwe_len(), n);
+            });
+        }
+        ggsw_node_host(ctx, GGSW_EP, ggsw_list, ggsw_count, base_log, level, ggsw_indexes, nullptr, glwe_in,
+                       glwe_inout, count);
+    });
+}
+
+int tfhe_mi355_ggsw_external_product_async(TfheMi355Context *ctx, const void *d_fourier_ggsw, size_t ggsw_count,
+                                           uint32_t base_log, uint32_t level, const uint32_t *d_ggsw_indexes,
+                                           const uint64_t *d_glwe_in, uint64_t *d_glwe_inout, size_t count,
+                                           void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!d_fourier_ggsw && count) || (!d_glwe_in && count) || (!d_glwe_inout && count))
+            fail("null argument");
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        launch_ggsw_node_dev(ctx, GGSW_EP, (const double2 *)d_fourier_ggsw, ggsw_count, d_ggsw_indexes, base_log,
+                             level, nullptr, d_glwe_in, d_glwe_inout, count, (hipStream_t)stream);
+    });
+}
+
+int tfhe_mi355_ggsw_cmux(TfheMi355Context *ctx, const uint64_t *ggsw_list, size_t ggsw_count, uint32_t base_log,
+                         uint32_t level, const uint32_t *ggsw_indexes, const uint64_t *ct0, const uint64_t *ct1,
+                         uint64_t *out, size_t count) {
+    return guarded([&] {
+        if (!ctx || (!ggsw_list && count) || (!ct0 && count) || (!ct1 && count) || (!out && count))
+            fail("null argument");
+        if (ctx->multi()) {
+            require_ggsw_shape(ctx, base_log, level);
+            validate_ggsw_indexes(ggsw_indexes, count, ggsw_count);
+            return split_rows(ctx, count, [&](TfheMi355Context *s, size_t a, size_t n) {
+                return tfhe_mi355_ggsw_cmux(s, ggsw_share(ctx, ggsw_list, ggsw_indexes, level, a),
+                                            ggsw_indexes ? ggsw_count : n, base_log, level,
+                                            ggsw_indexes ? ggsw_indexes + a : nullptr, ct0 + a * ctx->glwe_len(),
+                                            ct1 + a * ctx->glwe_len(), out + a * ctx->glwe_len(), n);
+            });
+        }
+        ggsw_node_host(ctx, GGSW_CMUX, ggsw_list, ggsw_count, base_log, level, ggsw_indexes, ct0, ct1, out, count);
+    });
+}
+
+int tfhe_mi355_ggsw_cmux_async(TfheMi355Context *ctx, const void *d_fourier_ggsw, size_t ggsw_count,
+                               uint32_t base_log, uint32_t level, const uint32_t *d_ggsw_indexes,
+                               const uint64_t *d_ct0, const uint64_t *d_ct1, uint64_t *d_out, size_t count,
+                               void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!d_fourier_ggsw && count) || (!d_ct0 && count) || (!d_ct1 && count) || (!d_out && count))
+            fail("null argument");
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        launch_ggsw_node_dev(ctx, GGSW_CMUX, (const double2 *)d_fourier_ggsw, ggsw_count, d_ggsw_indexes, base_log,
+                             level, d_ct0, d_ct1, d_out, count, (hipStream_t)stream);
+    });
+}
+
+int tfhe_mi355_ggsw_list_fourier_bytes(TfheMi355Context *ctx, size_t ggsw_count, uint32_t level, size_t *bytes) {
+    return guarded([&] {
+        ctx = primary(ctx);
+        if (!ctx || !bytes) fail("null argument");
+        if (level == 0 || level > 32) fail("GGSW level %u out of range", level);
+        *bytes = ggsw_count * ggsw_fourier_bytes(ctx, level);
+    });
+}
+
+int tfhe_mi355_ggsw_list_convert_async(TfheMi355Context *ctx, const uint64_t *d_ggsw_list, size_t ggsw_count,
+                                       uint32_t level, void *d_fourier_ggsw, void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!d_ggsw_list && ggsw_count) || (!d_fourier_ggsw && ggsw_count)) fail("null argument");
+        require_ggsw_shape(ctx, 1, level);
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        ggsw_list_to_fourier_dev(ctx, d_ggsw_list, (double2 *)d_fourier_ggsw, ggsw_count, level, (hipStream_t)stream);
+    });
+}
+
+int tfhe_mi355_vertical_packing_scratch(TfheMi355Context *ctx, size_t npoly, size_t count, size_t *bytes) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || !bytes) fail("null argument");
+        if (npoly == 0 || npoly > 0x40000000u || !is_pow2((uint32_t)npoly))
+            fail("vertical packing: the LUT has %zu polynomials, not a power of two", npoly);
+        *bytes = vp_scratch_bytes(ctx, npoly, count);
+    });
+}
+
+int tfhe_mi355_vertical_packing_async(TfheMi355Context *ctx, const void *d_fourier_ggsw, uint32_t base_log,
+                                      uint32_t level, uint32_t nbits, const uint64_t *d_luts, size_t lut_count,
+                                      size_t npoly, const uint32_t *d_lut_indexes, size_t count, uint64_t *d_lwe_out,
+                                      void *d_scratch, size_t scratch_bytes, void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!d_fourier_ggsw && count) || !d_luts || (!d_lwe_out && count)) fail("null argument");
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        launch_vertical_packing_dev(ctx, (const double2 *)d_fourier_ggsw, base_log, level, nbits, d_luts, lut_count,
+                                    npoly, d_lut_indexes, count, d_lwe_out, d_scratch, scratch_bytes,
+                                    (hipStream_t)stream);
+    });
+}
+
+int tfhe_mi355_vertical_packing(TfheMi355Context *ctx, const uint64_t *ggsw_list, uint32_t base_log, uint32_t level,
+                                uint32_t nbits, const uint64_t *luts, size_t lut_count, size_t npoly,
+                                const uint32_t *lut_indexes, size_t count, uint64_t *lwe_out) {
+    return guarded([&] {
+        if (!ctx || (!ggsw_list && count) || !luts || (!lwe_out && count)) fail("null argument");
+        if (ctx->multi()) {
+            const size_t per_item = (size_t)nbits * ggsw_std_words(ctx, level <= 32 ? level : 0);
+            return split_rows(ctx, count, [&](TfheMi355Context *s, size_t a, size_t n) {
+                return tfhe_mi355_vertical_packing(s, ggsw_list + a * per_item, base_log, level, nbits, luts, lut_count,
+                                                   npoly, lut_indexes ? lut_indexes + a : nullptr, n,
+                                                   lwe_out + a * (ctx->big_dim() + 1));
+            });
+        }
+        std::lock_guard<std::mutex> g(ctx->mu);
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        require_ggsw_shape(ctx, base_log, level);
+        vp_shape(ctx, nbits, npoly);
+        if (lut_count == 0) fail("lut_count out of range");
+        validate_lut_indexes(lut_indexes, count, lut_count);
+        if (count == 0) return;
+        // items in chunks of at most ~256 MiB of standard-domain GGSWs (each item brings nbits of them)
+        const size_t item_std = (size_t)nbits * ggsw_std_words(ctx, level) * 8;
+        const size_t item_f = (size_t)nbits * ggsw_fourier_bytes(ctx, level);
+        const size_t chunk = std::min(count, std::max<size_t>(1, ((size_t)256 << 20) / item_std));
+        const size_t lut_b = lut_count * npoly * ctx->N() * 8, out_w = ctx->big_dim() + 1;
+        DeviceBuffer d_std, d_f, d_luts, d_idx, d_out, d_scr;
+        d_std.reserve(chunk * item_std);
+        d_f.reserve(chunk * item_f);
+        d_luts.reserve(lut_b);
+        d_out.reserve(chunk * out_w * 8);
+        d_scr.reserve(std::max<size_t>(vp_scratch_bytes(ctx, npoly, chunk), 256));
+        if (lut_indexes) d_idx.reserve(chunk * 4);
+        hipStream_t s = ctx->stream;
+        check(hipMemcpyAsync(d_luts.ptr, luts, lut_b, hipMemcpyHostToDevice, s), "H2D luts");
+        for (size_t a = 0; a < count; a += chunk) {
+            const size_t n = std::min(chunk, count - a);
+            check(hipMemcpyAsync(d_std.ptr, ggsw_list + a * (item_std / 8), n * item_std, hipMemcpyHostToDevice, s),
+                  "H2D GGSW list");
+            if (lut_indexes)
+                check(hipMemcpyAsync(d_idx.ptr, lut_indexes + a, n * 4, hipMemcpyHostToDevice, s), "H2D lut indexes");
+            ggsw_list_to_fourier_dev(ctx, (const uint64_t *)d_std.ptr, (double2 *)d_f.ptr, n * nbits, level, s);
+            launch_vertical_packing_dev(ctx, (const double2 *)d_f.ptr, base_log, level, nbits,
+                                        (const uint64_t *)d_luts.ptr, lut_count, npoly, (const uint32_t *)d_idx.ptr, n,
+                                        (uint64_t *)d_out.ptr, d_scr.ptr, d_scr.bytes, s);
+            check(hipMemcpyAsync(lwe_out + a * out_w, d_out.ptr, n * out_w * 8, hipMemcpyDeviceToHost, s), "D2H out");
+            check(hipStreamSynchronize(s), "vertical packing sync");
+        }
     });
 }
 

@@ -250,6 +250,37 @@ struct GlwePolyMulLaunch {
 };
 hipError_t launch_glwe_poly_mul(const GlwePolyMulLaunch &a, hipStream_t s);
 
+// Batched GGSW x GLWE nodes (ggsw_ops.hip): out = base + G (x) d per node, every node with its own
+// Fourier GGSW and the decomposition (base_log, level; base_log * level <= 32) of the call.
+//   GGSW_EP    d = in1 (glwe_in), base = out (accumulated)      add_external_product_assign
+//   GGSW_CMUX  d = in1 - in0, base = in0 (out == in0 allowed)    cmux
+//   GGSW_ROT   d = in0 / X^rot - in0, base = in0                 one step of blind_rotate_assign (wop_pbs)
+// Node nd belongs to item nd / nodes_per_item and uses GGSW (block(item) * ggsw_per_item + ggsw_sel)
+// with block(item) = ggsw_indexes[item] (clamped to ggsw_blocks - 1) or item.  Its operands sit at
+// in0 / in1 + nd * in_stride words, its output at out + nd * (k+1)N (or nd * (kN+1) when extract:
+// degree-0 sample extraction of the result).  leaf: the operands are trivial GLWEs (zero mask) whose
+// bodies are polynomials of the item's LUT, in0 = luts [lut_count][npoly][N]: polynomials 2s, 2s+1
+// for node s of the item (CMUX), polynomial s (ROT).
+enum GgswMode { GGSW_EP = 0, GGSW_CMUX = 1, GGSW_ROT = 2 };
+struct GgswCmuxLaunch {
+    const double2 *fggsw;          // [ggsw_blocks][ggsw_per_item][L][k+1][k+1] polys, engine Fourier layout
+    const uint32_t *ggsw_indexes;  // [items] or null
+    size_t ggsw_blocks;
+    int ggsw_per_item, ggsw_sel;
+    const uint64_t *in0, *in1;
+    uint64_t *out;
+    const uint32_t *lut_indexes;   // leaf: [items] or null; entries >= lut_count read LUT lut_count-1
+    uint32_t lut_count;
+    int npoly;                     // leaf: polynomials per LUT
+    int mode, leaf, rot, extract;
+    size_t nodes, nodes_per_item;
+    size_t in_stride;
+    int base_log, level;
+    const double2 *W, *twist;
+};
+bool ggsw_ops_supported(int N, int k);
+hipError_t launch_ggsw_cmux(int N, int k, const GgswCmuxLaunch &a, hipStream_t s);
+
 // seeded-key decompression (csprng.hip): AES-CTR mask stream of the compression seed written as
 // `row_words` mask words per row, followed by `body_words` copied from d_bodies, for `rows` rows
 size_t aes_tables_bytes();

@@ -108,6 +108,21 @@ SIGNATURES = [
     ("tfhe_mi355_packing_keyswitch_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
     ("tfhe_mi355_glwe_poly_mul", ctypes.c_int, [vp, u64p, sz, u64p, sz, sz, ctypes.c_int, u64p]),
     ("tfhe_mi355_glwe_poly_mul_async", ctypes.c_int, [vp, vp, sz, vp, sz, sz, ctypes.c_int, vp, vp]),
+    ("tfhe_mi355_ggsw_external_product", ctypes.c_int,
+     [vp, u64p, sz, ctypes.c_uint32, ctypes.c_uint32, u32p, u64p, u64p, sz]),
+    ("tfhe_mi355_ggsw_external_product_async", ctypes.c_int,
+     [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, sz, vp]),
+    ("tfhe_mi355_ggsw_cmux", ctypes.c_int,
+     [vp, u64p, sz, ctypes.c_uint32, ctypes.c_uint32, u32p, u64p, u64p, u64p, sz]),
+    ("tfhe_mi355_ggsw_cmux_async", ctypes.c_int,
+     [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, sz, vp]),
+    ("tfhe_mi355_ggsw_list_fourier_bytes", ctypes.c_int, [vp, sz, ctypes.c_uint32, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_ggsw_list_convert_async", ctypes.c_int, [vp, vp, sz, ctypes.c_uint32, vp, vp]),
+    ("tfhe_mi355_vertical_packing", ctypes.c_int,
+     [vp, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u64p, sz, sz, u32p, sz, u64p]),
+    ("tfhe_mi355_vertical_packing_async", ctypes.c_int,
+     [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, sz, sz, vp, sz, vp, vp, sz, vp]),
+    ("tfhe_mi355_vertical_packing_scratch", ctypes.c_int, [vp, sz, sz, ctypes.POINTER(sz)]),
     ("tfhe_mi355_client_gen_packing_keyswitch_key", ctypes.c_int,
      [ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_double, u64p, ctypes.c_uint32]),

@@ -37,6 +37,20 @@ def gen_bootstrap_key(seed, lwe_sk, glwe_sk, glwe_dimension, polynomial_size, ba
     return bsk
 
 
+def gen_ggsw_list(seed, bits, glwe_sk, glwe_dimension, polynomial_size, base_log, level, std_dev,
+                  threads: int = 0) -> np.ndarray:
+    """GGSW encryptions of the constant polynomials `bits[i]`, [len(bits)][level][k+1][(k+1)N]
+    (encrypt_constant_ggsw_ciphertext, ggsw_encryption.rs:116-150), levels stored 1..L.
+
+    A bootstrap key is exactly that list for the bits of an LWE key (lwe_bootstrap_key_generation.rs:
+    one constant GGSW per key bit), so this is gen_bootstrap_key with `bits` in the LWE key's place;
+    any decomposition may be asked for, e.g. the circuit-bootstrap one of the WoP-PBS sets."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint64).ravel()
+    k, N = glwe_dimension, polynomial_size
+    out = gen_bootstrap_key(seed, bits, glwe_sk, k, N, base_log, level, std_dev, threads)
+    return out.reshape(len(bits), level, k + 1, (k + 1) * N)
+
+
 def gen_multi_bit_bootstrap_key(seed, lwe_sk, glwe_sk, glwe_dimension, polynomial_size, base_log, level,
                                 grouping_factor, std_dev, threads: int = 0) -> np.ndarray:
     """[n/g][2^g][L][k+1][k+1][N] (lwe_multi_bit_bootstrap_key_generation.rs:87-173)."""

@@ -357,6 +357,71 @@ class Engine:
         _lib.call("tfhe_mi355_glwe_poly_mul", self._h, _ptr(g), J, _ptr(v), v.shape[0], count, int(extract), _ptr(out))
         return out
 
+    # -- GGSW operations: per-item GGSW ciphertexts, decomposition chosen per call -----------
+    def ggsw_words(self, level: int) -> int:
+        """u64 words of one standard-domain GGSW: [level][k+1][(k+1)N]."""
+        k1 = self.params.glwe_dimension + 1
+        return level * k1 * k1 * self.params.polynomial_size
+
+    def _ggsw_list(self, ggsw_list, level: int) -> np.ndarray:
+        g = _u64(ggsw_list)
+        if g.size == 0 or g.size % self.ggsw_words(level):
+            raise ValueError(f"GGSW list of {g.size} words is no multiple of {self.ggsw_words(level)}")
+        return g.reshape(-1, self.ggsw_words(level))
+
+    def ggsw_external_product(self, ggsw_list, base_log: int, level: int, glwe_in, glwe_inout,
+                              ggsw_indexes=None) -> np.ndarray:
+        """glwe_inout[i] += ggsw[i] (x) glwe_in[i] (add_external_product_assign, fft64/crypto/ggsw.rs:
+        477-598), batched; returns the accumulated array (glwe_inout itself when it is a C-contiguous
+        uint64 array).  ggsw_indexes picks each item's GGSW (None: item i uses GGSW i)."""
+        g = self._ggsw_list(ggsw_list, level)
+        x = _u64(glwe_in).reshape(-1, self.glwe_len)
+        out = _u64(glwe_inout).reshape(-1, self.glwe_len)
+        if out.shape != x.shape:
+            raise ValueError("ggsw_external_product: glwe_in and glwe_inout differ in shape")
+        idx, idxp = self._idx(ggsw_indexes, x.shape[0], g.shape[0])
+        _lib.call("tfhe_mi355_ggsw_external_product", self._h, _ptr(g), g.shape[0], base_log, level, idxp, _ptr(x),
+                  _ptr(out), x.shape[0])
+        return out
+
+    def ggsw_cmux(self, ggsw_list, base_log: int, level: int, ct0, ct1, ggsw_indexes=None, out=None) -> np.ndarray:
+        """out[i] = ct0[i] + ggsw[i] (x) (ct1[i] - ct0[i]) (cmux, fft64/crypto/ggsw.rs:766-777), batched;
+        `out` may be ct0 itself."""
+        g = self._ggsw_list(ggsw_list, level)
+        a = _u64(ct0).reshape(-1, self.glwe_len)
+        b = _u64(ct1).reshape(-1, self.glwe_len)
+        if a.shape != b.shape:
+            raise ValueError("ggsw_cmux: ct0 and ct1 differ in shape")
+        idx, idxp = self._idx(ggsw_indexes, a.shape[0], g.shape[0])
+        out = self._out(out, a.shape)
+        _lib.call("tfhe_mi355_ggsw_cmux", self._h, _ptr(g), g.shape[0], base_log, level, idxp, _ptr(a), _ptr(b),
+                  _ptr(out), a.shape[0])
+        return out
+
+    def vertical_packing(self, ggsw_list, base_log: int, level: int, luts, lut_indexes=None) -> np.ndarray:
+        """vertical_packing (fft64/crypto/wop_pbs/mod.rs:785-853), batched: ggsw_list [count][nbits]
+        GGSWs (index bits, most significant first), luts [lut_count][npoly][N] (or [npoly][N]);
+        returns [count][kN+1]."""
+        N = self.params.polynomial_size
+        g = _u64(ggsw_list)
+        if g.ndim < 2:
+            raise ValueError("vertical_packing: ggsw_list must be [count][nbits] GGSWs")
+        count = g.shape[0]
+        g = g.reshape(count, -1)
+        if g.shape[1] == 0 or g.shape[1] % self.ggsw_words(level):
+            raise ValueError(f"vertical_packing: {g.shape[1]} words per item is no multiple of one GGSW")
+        nbits = g.shape[1] // self.ggsw_words(level)
+        L = _u64(luts)
+        if L.ndim == 2:
+            L = L.reshape(1, *L.shape)
+        if L.ndim != 3 or L.shape[2] != N:
+            raise ValueError("vertical_packing: luts must be [lut_count][npoly][N]")
+        idx, idxp = self._idx(lut_indexes, count, L.shape[0])
+        out = np.empty((count, self.big_dim + 1), dtype=np.uint64)
+        _lib.call("tfhe_mi355_vertical_packing", self._h, _ptr(g), base_log, level, nbits, _ptr(L), L.shape[0],
+                  L.shape[1], idxp, count, _ptr(out))
+        return out
+
     # -- device (torch) async ops -------------------------------------------------------
     # Every device scratch the C ABI needs comes from the caller (include/tfhe_mi355.h): pass
     # d_scratch (>= the matching *_scratch_bytes), or let these wrappers allocate it from torch's
@@ -449,6 +514,39 @@ class Engine:
                             d_out, stream=None) -> None:
         _lib.call("tfhe_mi355_glwe_poly_mul_async", self._h, _dev_ptr(d_glwe), glwe_per_item, _dev_ptr(d_polys),
                   npoly, count, int(extract), _dev_ptr(d_out), _stream_ptr(stream))
+
+    def ggsw_list_fourier_bytes(self, ggsw_count: int, level: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call("tfhe_mi355_ggsw_list_fourier_bytes", self._h, ggsw_count, level, ctypes.byref(b))
+        return b.value
+
+    def ggsw_list_convert_async(self, d_ggsw_list, ggsw_count: int, level: int, d_fourier, stream=None) -> None:
+        """Standard -> Fourier GGSW list on the device, for the async forms below."""
+        _lib.call("tfhe_mi355_ggsw_list_convert_async", self._h, _dev_ptr(d_ggsw_list), ggsw_count, level,
+                  _dev_ptr(d_fourier), _stream_ptr(stream))
+
+    def ggsw_external_product_async(self, d_fourier, ggsw_count: int, base_log: int, level: int, d_glwe_in,
+                                    d_glwe_inout, count: int, d_ggsw_indexes=None, stream=None) -> None:
+        _lib.call("tfhe_mi355_ggsw_external_product_async", self._h, _dev_ptr(d_fourier), ggsw_count, base_log, level,
+                  _dev_ptr(d_ggsw_indexes), _dev_ptr(d_glwe_in), _dev_ptr(d_glwe_inout), count, _stream_ptr(stream))
+
+    def ggsw_cmux_async(self, d_fourier, ggsw_count: int, base_log: int, level: int, d_ct0, d_ct1, d_out,
+                        count: int, d_ggsw_indexes=None, stream=None) -> None:
+        _lib.call("tfhe_mi355_ggsw_cmux_async", self._h, _dev_ptr(d_fourier), ggsw_count, base_log, level,
+                  _dev_ptr(d_ggsw_indexes), _dev_ptr(d_ct0), _dev_ptr(d_ct1), _dev_ptr(d_out), count,
+                  _stream_ptr(stream))
+
+    def vertical_packing_scratch_bytes(self, npoly: int, count: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call("tfhe_mi355_vertical_packing_scratch", self._h, npoly, count, ctypes.byref(b))
+        return b.value
+
+    def vertical_packing_async(self, d_fourier, base_log: int, level: int, nbits: int, d_luts, lut_count: int,
+                               npoly: int, count: int, d_out, d_lut_indexes=None, stream=None, d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.vertical_packing_scratch_bytes(npoly, count), stream)
+        _lib.call("tfhe_mi355_vertical_packing_async", self._h, _dev_ptr(d_fourier), base_log, level, nbits,
+                  _dev_ptr(d_luts), lut_count, npoly, _dev_ptr(d_lut_indexes), count, _dev_ptr(d_out), sp, sb,
+                  _stream_ptr(stream))
 
 
 def fill_accumulator(params: ClassicPBSParameters, f) -> np.ndarray:
