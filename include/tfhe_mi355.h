@@ -408,6 +408,71 @@ int tfhe_mi355_vertical_packing_async(TfheMi355Context *ctx, const void *d_fouri
                                       void *d_scratch, size_t scratch_bytes, void *stream);
 int tfhe_mi355_vertical_packing_scratch(TfheMi355Context *ctx, size_t npoly, size_t count, size_t *bytes);
 
+/* The bootstrapped half of WoP-PBS: LWE ciphertexts in, looked-up LWE ciphertexts out, all on the
+ * device (extract_bits -> circuit_bootstrap_boolean -> vertical_packing,
+ * fft_impl/fft64/crypto/wop_pbs/mod.rs:66-225, 243-444, 647-746).  It needs a classic PBS shape with
+ * N <= 2048 and k <= 5, the context's bootstrapping and keyswitching keys, and the private functional
+ * packing keyswitching keys:
+ *
+ * pfpksk list: the reference's LwePrivateFunctionalPackingKeyswitchKeyList memory as it is,
+ * [k+1 keys][k*N+1 input blocks][level][(k+1)*N], level 1 first (the opposite of the keyswitching and
+ * packing keys' L..1 order: no flipping by the caller).  Its decomposition belongs to the key:
+ * 1 <= base_log <= 31, level >= 1, base_log * level <= 63.  A multi-device context uploads it to every
+ * device. */
+int tfhe_mi355_pfpksk_list_upload(TfheMi355Context *ctx, const uint64_t *pfpksk, size_t len, uint32_t base_log,
+                                  uint32_t level);
+/* private_functional_keyswitch_lwe_ciphertext_into_glwe_ciphertext
+ * (lwe_private_functional_packing_keyswitch.rs:21-89) under every key of the list:
+ * lwe_in [count][k*N+1] -> glwe_out [count][k+1][(k+1)*N],
+ * glwe_out[c][g] = - sum_i sum_lvl digit_lvl(lwe_in[c][i]) * key_g[i][lvl], the body (i = k*N) decomposed
+ * like the mask words and not added to the output.  base_log <= 15 runs as int8 MFMA GEMMs on byte
+ * planes repacked at upload, wider digits in a 64-bit integer kernel; both are exact.  The scratch
+ * query fails until the keys are uploaded. */
+int tfhe_mi355_private_functional_packing_keyswitch(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *glwe_out,
+                                                    size_t count);
+int tfhe_mi355_private_functional_packing_keyswitch_async(TfheMi355Context *ctx, const uint64_t *d_lwe_in,
+                                                          uint64_t *d_glwe_out, size_t count, void *d_scratch,
+                                                          size_t scratch_bytes, void *stream);
+int tfhe_mi355_private_functional_packing_keyswitch_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+/* extract_bits (wop_pbs/mod.rs:66-225): lwe_in [count][k*N+1] -> lwe_out [count][nbits][n+1], the bits
+ * delta_log .. delta_log + nbits - 1 of every message, most significant first, each scaled to q/2 and
+ * under the small LWE key.  Fails when delta_log + nbits > 64, nbits = 0, or delta_log = 0 with
+ * nbits > 1 (the reference's shift underflows there). */
+int tfhe_mi355_extract_bits(TfheMi355Context *ctx, const uint64_t *lwe_in, uint32_t delta_log, uint32_t nbits,
+                            uint64_t *lwe_out, size_t count);
+int tfhe_mi355_extract_bits_async(TfheMi355Context *ctx, const uint64_t *d_lwe_in, uint32_t delta_log, uint32_t nbits,
+                                  uint64_t *d_lwe_out, size_t count, void *d_scratch, size_t scratch_bytes,
+                                  void *stream);
+int tfhe_mi355_extract_bits_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+/* circuit_bootstrap_boolean (wop_pbs/mod.rs:243-444): lwe_in [count][n+1], one bit at 2^delta_log each
+ * -> ggsw_out [count][cbs_level][k+1][(k+1)*N], standard domain, the layout
+ * tfhe_mi355_ggsw_list_convert_async and the host-pointer GGSW calls take.  One PBS launch over
+ * count * cbs_level rows and one pfpks launch over the same rows.  cbs_base_log * cbs_level <= 32. */
+int tfhe_mi355_circuit_bootstrap(TfheMi355Context *ctx, const uint64_t *lwe_in, uint32_t delta_log,
+                                 uint32_t cbs_base_log, uint32_t cbs_level, uint64_t *ggsw_out, size_t count);
+int tfhe_mi355_circuit_bootstrap_async(TfheMi355Context *ctx, const uint64_t *d_lwe_in, uint32_t delta_log,
+                                       uint32_t cbs_base_log, uint32_t cbs_level, uint64_t *d_ggsw_out, size_t count,
+                                       void *d_scratch, size_t scratch_bytes, void *stream);
+int tfhe_mi355_circuit_bootstrap_scratch(TfheMi355Context *ctx, uint32_t cbs_level, size_t count, size_t *bytes);
+/* circuit_bootstrap_boolean_vertical_packing (wop_pbs/mod.rs:647-746): lwe_in [count][nbits][n+1], one
+ * bit per ciphertext at q/2, most significant first (what tfhe_mi355_extract_bits writes);
+ * luts [lut_count][nout][npoly][N] with lut_indexes [count] (NULL: LUT 0); lwe_out [count][nout][k*N+1].
+ * Circuit bootstrap, Fourier conversion, then one vertical packing per output o on polynomials
+ * [o*npoly, (o+1)*npoly) of the item's LUT, under the same GGSWs. */
+int tfhe_mi355_circuit_bootstrap_vertical_packing(TfheMi355Context *ctx, const uint64_t *lwe_in, uint32_t nbits,
+                                                  uint32_t cbs_base_log, uint32_t cbs_level, const uint64_t *luts,
+                                                  size_t lut_count, size_t nout, size_t npoly,
+                                                  const uint32_t *lut_indexes, size_t count, uint64_t *lwe_out);
+int tfhe_mi355_circuit_bootstrap_vertical_packing_async(TfheMi355Context *ctx, const uint64_t *d_lwe_in, uint32_t nbits,
+                                                        uint32_t cbs_base_log, uint32_t cbs_level,
+                                                        const uint64_t *d_luts, size_t lut_count, size_t nout,
+                                                        size_t npoly, const uint32_t *d_lut_indexes, size_t count,
+                                                        uint64_t *d_lwe_out, void *d_scratch, size_t scratch_bytes,
+                                                        void *stream);
+int tfhe_mi355_circuit_bootstrap_vertical_packing_scratch(TfheMi355Context *ctx, uint32_t nbits, uint32_t cbs_level,
+                                                          size_t lut_count, size_t nout, size_t npoly, size_t count,
+                                                          size_t *bytes);
+
 /* Batched LWE keyswitch (big key -> small key): lwe_in count x (k*N+1) -> lwe_out count x (n+1).
  * Replaces keyswitch_lwe_ciphertext (lwe_keyswitch.rs:96-170). */
 int tfhe_mi355_keyswitch(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *lwe_out, size_t count);
@@ -492,6 +557,12 @@ int tfhe_mi355_client_gen_packing_keyswitch_key(uint64_t seed, const uint64_t *i
                                                 const uint64_t *glwe_sk, uint32_t k, uint32_t N,
                                                 uint32_t base_log, uint32_t level, double std_dev,
                                                 uint64_t *pksk, uint32_t threads);
+/* pfpksk list of the circuit bootstrap [k+1][in_dim+1][level][(k+1)N], level 1 first (lwe_wopbs.rs:80-158):
+ * key g, block i, level lvl encrypts -s_i * P_g * 2^(64 - base_log*lvl); s_(in_dim) = -1 (the body),
+ * P_g = polynomial g of the GLWE key (g < k) or the constant -1 (g = k) */
+int tfhe_mi355_client_gen_pfpksk_list(uint64_t seed, const uint64_t *in_sk, uint32_t in_dim, const uint64_t *glwe_sk,
+                                      uint32_t k, uint32_t N, uint32_t base_log, uint32_t level, double std_dev,
+                                      uint64_t *pfpksk, uint32_t threads);
 /* seeded keys (masks from the AES-CTR stream of mask_seed, noise from noise_seed); bodies only */
 int tfhe_mi355_client_gen_seeded_bootstrap_key(uint64_t noise_seed, uint64_t mask_seed_lo, uint64_t mask_seed_hi,
                                                const uint64_t *lwe_sk, uint32_t n, const uint64_t *glwe_sk,

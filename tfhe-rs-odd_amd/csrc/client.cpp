@@ -340,6 +340,49 @@ int tfhe_mi355_client_gen_packing_keyswitch_key(uint64_t seed, const uint64_t *i
     });
 }
 
+// Private functional packing keyswitching keys of the circuit bootstrap
+// [k+1 keys][in_dim+1 blocks][level][(k+1)N], level 1 first (lwe_wopbs.rs:80-158,
+// lwe_private_functional_packing_keyswitch_key_generation.rs:19-134): key g, block i, level lvl is a
+// GLWE encryption of -s_i * P_g * 2^(64 - base_log*lvl), with s_(in_dim) = -1 standing for the body,
+// P_g the g-th polynomial of the GLWE key for g < k and the constant -1 for g = k.  Every (key, block)
+// draws from its own stream.
+int tfhe_mi355_client_gen_pfpksk_list(uint64_t seed, const uint64_t *in_sk, uint32_t in_dim, const uint64_t *glwe_sk,
+                                      uint32_t k, uint32_t N, uint32_t base_log, uint32_t level, double std,
+                                      uint64_t *pfpksk, uint32_t threads) {
+    return guard([&] {
+        if (!in_sk || !glwe_sk || !pfpksk) throw std::invalid_argument("null argument");
+        if (level == 0 || base_log == 0 || base_log > 31 || base_log * level > 63)
+            throw std::invalid_argument("invalid decomposition");
+        const size_t glwe_len = (size_t)(k + 1) * N, blocks = (size_t)in_dim + 1;
+        std::atomic<size_t> next{0};
+        auto work = [&] {
+            for (;;) {
+                const size_t t = next++;
+                if (t >= (size_t)(k + 1) * blocks) break;
+                const size_t g = t / blocks, i = t % blocks;
+                Rng r(seed, 0x8000000ULL + t);
+                const uint64_t si = i < in_dim ? in_sk[i] : ~0ULL;
+                for (uint32_t lvl = 1; lvl <= level; lvl++) {
+                    uint64_t *ct = pfpksk + (t * level + (lvl - 1)) * glwe_len;
+                    uint64_t *body = ct + (size_t)k * N;
+                    const uint64_t factor = (0 - si) << (64 - base_log * lvl);
+                    std::memset(body, 0, sizeof(uint64_t) * N);
+                    if (g < k)
+                        for (uint32_t j = 0; j < N; j++) body[j] = glwe_sk[g * N + j] * factor;
+                    else
+                        body[0] = 0 - factor;
+                    glwe_encrypt_assign(r, ct, glwe_sk, (int)k, (int)N, std);
+                }
+            }
+        };
+        uint32_t nt = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
+        std::vector<std::thread> th;
+        for (uint32_t t = 1; t < nt; t++) th.emplace_back(work);
+        work();
+        for (auto &t : th) t.join();
+    });
+}
+
 // Seeded keys (the reference's SeededLweBootstrapKey / SeededLweKeyswitchKey with a
 // CompressionSeed, seeded_lwe_bootstrap_key_generation.rs, seeded_lwe_keyswitch_key_generation.rs):
 // masks from the AES-CTR stream of (mask_seed_lo, mask_seed_hi), noise from the engine's own RNG;

@@ -228,6 +228,43 @@ size_t ks_mfma_scratch_bytes(int in_dim, int level, int count);
 hipError_t launch_ksk_repack(const uint64_t *ksk, int8_t *kt, int in_dim, int level, int out_dim, hipStream_t s);
 hipError_t launch_keyswitch_mfma(const KeyswitchLaunch &a, const int8_t *kt, void *scratch, hipStream_t s);
 
+// Private functional packing keyswitch with every key of a pfpksk list (pfpks.hip):
+//   glwe_out[c][g][j] = - sum_{i < in_rows} sum_{lvl} digit_lvl(lwe_in[c][i]) * key[g][i][lvl-1][j]
+// the input body (i = kN) is decomposed like the mask words and nothing is added to the output.
+struct PfpksLaunch {
+    const uint64_t *lwe_in;  // [count][in_rows]
+    uint64_t *glwe_out;      // [count][ncols]
+    const uint64_t *key;     // [k+1][in_rows][level][glwe], level 1 first (the reference's order)
+    int in_rows;             // kN + 1
+    int glwe;                // (k+1)N, a multiple of 64
+    int ncols;               // (k+1) * glwe
+    int base_log, level;     // 1 <= base_log <= 31, base_log * level <= 63
+    int count;
+};
+hipError_t launch_pfpks(const PfpksLaunch &a, hipStream_t s);
+// int8-MFMA form (base_log <= 15): key repacked once into 8 byte planes (pfpks_mfma_cols x pfpks_mfma_rows each)
+bool pfpks_mfma_supported(int in_rows, int level, int base_log);
+size_t pfpks_mfma_rows(int in_rows, int level);
+size_t pfpks_mfma_cols(int ncols);
+size_t pfpks_mfma_scratch_bytes(int in_rows, int level, int count);
+hipError_t launch_pfpksk_repack(const uint64_t *key, int8_t *kt, int keys, int in_rows, int level, int glwe,
+                                hipStream_t s);
+hipError_t launch_pfpks_mfma(const PfpksLaunch &a, const int8_t *kt, void *scratch, hipStream_t s);
+
+// elementwise glue of bit extraction and circuit bootstrap (lwe_ops.hip, wop_pbs/mod.rs:158-224, 369-444)
+//   shift_rows: dst[r][w] = (src[r / reps][w] << shift) + (w == words - 1 ? body_add : 0), dst rows dst_stride apart
+//   add_body:   buf[r][words - 1] += 2^(first - step * (r % mod))
+//   sub_rows:   cur[r][w] -= x[r][w] + (w == words - 1 ? body_add : 0)
+//   fill_luts:  luts[l] = trivial GLWE whose body is all -2^(first - step * l); lut_indexes[r] = r % nluts
+hipError_t launch_wop_shift_rows(uint64_t *dst, const uint64_t *src, size_t rows, size_t words, size_t dst_stride,
+                                 size_t reps, int shift, uint64_t body_add, hipStream_t s);
+hipError_t launch_wop_add_body(uint64_t *buf, size_t rows, size_t words, int first, int step, size_t mod,
+                               hipStream_t s);
+hipError_t launch_wop_sub_rows(uint64_t *cur, const uint64_t *x, size_t rows, size_t words, uint64_t body_add,
+                               hipStream_t s);
+hipError_t launch_wop_fill_luts(uint64_t *luts, size_t nluts, size_t glwe, size_t body_off, int first, int step,
+                                uint32_t *lut_indexes, size_t rows, hipStream_t s);
+
 // batched LWE linear algebra / trivial PBS (lwe_ops.hip)
 hipError_t launch_torus_from_fraction(const double *fr, uint64_t *acc, uint64_t *set, size_t n, hipStream_t s);
 hipError_t launch_lwe_scalar_mul_add(uint64_t *y, const uint64_t *x, uint64_t scalar, size_t rows, size_t words,

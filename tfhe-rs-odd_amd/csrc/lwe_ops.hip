@@ -8,6 +8,8 @@
 //   the bivariate packing  left = left * factor + right  (shortint/server_key/bivariate_pbs.rs:167-182)
 //   trivial_pbs_assign     (shortint/server_key/mod.rs:763-781)
 // All arithmetic is wrapping mod 2^64, as the reference's.
+#include <algorithm>
+
 #include "engine.h"
 #include "fft_device.h"
 
@@ -49,6 +51,86 @@ __global__ void __launch_bounds__(256) torus_from_fraction_kernel(const double *
     torus_add_frac(c, fr[e], k32);
     acc[e] = c;
     set[e] = torus_from_frac(fr[e], k32);
+}
+
+// ---- glue of bit extraction and circuit bootstrap (wop_pbs/mod.rs:158-224, 369-444) ----------------
+// dst[r][w] = (src[r / reps][w] << shift) + (body ? body_add : 0): the shift on the padding bit
+// (extract_bits :160-166), the cleartext multiplication by 2^(63 - delta_log) with q/4 on the body,
+// one copy per circuit-bootstrap level (homomorphic_shift_boolean :398-407), and the store of the
+// keyswitch output into its slot of the output list (:182-184, shift 0)
+__global__ void __launch_bounds__(256) wop_shift_rows_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ src,
+                                                             size_t rows, size_t words, size_t dst_stride, size_t reps,
+                                                             int shift, uint64_t body_add) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows * words) return;
+    const size_t r = e / words, w = e % words;
+    dst[r * dst_stride + w] = (src[(r / reps) * words + w] << shift) + (w + 1 == words ? body_add : 0);
+}
+
+// body of row r += 2^(first - step * (r % mod))  (:194, :219, :442-443)
+__global__ void __launch_bounds__(256) wop_add_body_kernel(uint64_t *__restrict__ buf, size_t rows, size_t words,
+                                                           int first, int step, size_t mod) {
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    buf[r * words + words - 1] += (uint64_t)1 << (first - step * (int)(r % mod));
+}
+
+// cur -= x + (body ? body_add : 0)  (:219-223)
+__global__ void __launch_bounds__(256) wop_sub_rows_kernel(uint64_t *__restrict__ cur, const uint64_t *__restrict__ x,
+                                                           size_t rows, size_t words, uint64_t body_add) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows * words) return;
+    cur[e] -= x[e] + (e % words + 1 == words ? body_add : 0);
+}
+
+// LUT l = trivial GLWE, body all -2^(first - step * l) (:198-205, :423-427); lut_indexes[r] = r % nluts
+__global__ void __launch_bounds__(256) wop_fill_luts_kernel(uint64_t *__restrict__ luts, size_t nluts, size_t glwe,
+                                                            size_t body_off, int first, int step,
+                                                            uint32_t *__restrict__ lut_indexes, size_t rows) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < nluts * glwe) {
+        const size_t l = e / glwe, w = e % glwe;
+        luts[e] = w < body_off ? 0 : 0 - ((uint64_t)1 << (first - step * (int)l));
+    }
+    if (lut_indexes && e < rows) lut_indexes[e] = (uint32_t)(e % nluts);
+}
+
+hipError_t launch_wop_shift_rows(uint64_t *dst, const uint64_t *src, size_t rows, size_t words, size_t dst_stride,
+                                 size_t reps, int shift, uint64_t body_add, hipStream_t s) {
+    const size_t n = rows * words;
+    if (n == 0) return hipSuccess;
+    if (shift < 0 || shift > 63 || reps == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wop_shift_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, src, rows,
+                       words, dst_stride, reps, shift, body_add);
+    return hipGetLastError();
+}
+
+hipError_t launch_wop_add_body(uint64_t *buf, size_t rows, size_t words, int first, int step, size_t mod,
+                               hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    if (mod == 0 || first > 63 || first - step * (int)(mod - 1) < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wop_add_body_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, buf, rows, words,
+                       first, step, mod);
+    return hipGetLastError();
+}
+
+hipError_t launch_wop_sub_rows(uint64_t *cur, const uint64_t *x, size_t rows, size_t words, uint64_t body_add,
+                               hipStream_t s) {
+    const size_t n = rows * words;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(wop_sub_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cur, x, rows, words,
+                       body_add);
+    return hipGetLastError();
+}
+
+hipError_t launch_wop_fill_luts(uint64_t *luts, size_t nluts, size_t glwe, size_t body_off, int first, int step,
+                                uint32_t *lut_indexes, size_t rows, hipStream_t s) {
+    if (nluts == 0) return hipSuccess;
+    if (first > 63 || first - step * (int)(nluts - 1) < 0) return hipErrorInvalidValue;
+    const size_t n = std::max(nluts * glwe, lut_indexes ? rows : 0);
+    hipLaunchKernelGGL(wop_fill_luts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, luts, nluts, glwe,
+                       body_off, first, step, lut_indexes, rows);
+    return hipGetLastError();
 }
 
 hipError_t launch_torus_from_fraction(const double *fr, uint64_t *acc, uint64_t *set, size_t n, hipStream_t s) {

@@ -123,6 +123,28 @@ SIGNATURES = [
     ("tfhe_mi355_vertical_packing_async", ctypes.c_int,
      [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, sz, sz, vp, sz, vp, vp, sz, vp]),
     ("tfhe_mi355_vertical_packing_scratch", ctypes.c_int, [vp, sz, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_pfpksk_list_upload", ctypes.c_int, [vp, u64p, sz, ctypes.c_uint32, ctypes.c_uint32]),
+    ("tfhe_mi355_private_functional_packing_keyswitch", ctypes.c_int, [vp, u64p, u64p, sz]),
+    ("tfhe_mi355_private_functional_packing_keyswitch_async", ctypes.c_int, [vp, vp, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_private_functional_packing_keyswitch_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_extract_bits", ctypes.c_int, [vp, u64p, ctypes.c_uint32, ctypes.c_uint32, u64p, sz]),
+    ("tfhe_mi355_extract_bits_async", ctypes.c_int,
+     [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_extract_bits_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_circuit_bootstrap", ctypes.c_int,
+     [vp, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u64p, sz]),
+    ("tfhe_mi355_circuit_bootstrap_async", ctypes.c_int,
+     [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_circuit_bootstrap_scratch", ctypes.c_int, [vp, ctypes.c_uint32, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_circuit_bootstrap_vertical_packing", ctypes.c_int,
+     [vp, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u64p, sz, sz, sz, u32p, sz, u64p]),
+    ("tfhe_mi355_circuit_bootstrap_vertical_packing_async", ctypes.c_int,
+     [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, sz, sz, sz, vp, sz, vp, vp, sz, vp]),
+    ("tfhe_mi355_circuit_bootstrap_vertical_packing_scratch", ctypes.c_int,
+     [vp, ctypes.c_uint32, ctypes.c_uint32, sz, sz, sz, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_client_gen_pfpksk_list", ctypes.c_int,
+     [ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_double, u64p, ctypes.c_uint32]),
     ("tfhe_mi355_client_gen_packing_keyswitch_key", ctypes.c_int,
      [ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_double, u64p, ctypes.c_uint32]),

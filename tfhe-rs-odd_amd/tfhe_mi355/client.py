@@ -86,6 +86,21 @@ def gen_packing_keyswitch_key(seed, in_sk, glwe_sk, glwe_dimension, polynomial_s
     return out
 
 
+def gen_pfpksk_list(seed, in_sk, glwe_sk, glwe_dimension, polynomial_size, base_log, level, std_dev,
+                    threads: int = 0) -> np.ndarray:
+    """Private functional packing keyswitching keys of the circuit bootstrap
+    [k+1][in+1][level][(k+1)N], level 1 first (lwe_wopbs.rs:80-158)."""
+    in_sk = np.ascontiguousarray(in_sk, dtype=np.uint64)
+    glwe_sk = np.ascontiguousarray(glwe_sk, dtype=np.uint64)
+    k, N = glwe_dimension, polynomial_size
+    out = np.empty((k + 1) * (len(in_sk) + 1) * level * (k + 1) * N, dtype=np.uint64)
+    if threads <= 0:
+        threads = min(16, os.cpu_count() or 1)
+    _lib.call("tfhe_mi355_client_gen_pfpksk_list", seed, _ptr(in_sk), len(in_sk), _ptr(glwe_sk), k, N, base_log,
+              level, std_dev, _ptr(out), threads)
+    return out
+
+
 def _seed_parts(seed: int):
     return seed & 0xFFFFFFFFFFFFFFFF, (seed >> 64) & 0xFFFFFFFFFFFFFFFF
 

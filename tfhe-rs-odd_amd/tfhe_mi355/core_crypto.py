@@ -7,6 +7,11 @@
   add_external_product_assign                     lwe_programmable_bootstrapping.rs:309-473
   cmux_assign                                     lwe_programmable_bootstrapping.rs:552-763
   vertical_packing                                fft_impl/fft64/crypto/wop_pbs/mod.rs:785-853
+  private_functional_keyswitch_lwe_ciphertext_into_glwe_ciphertext
+                                                  lwe_private_functional_packing_keyswitch.rs:21-89
+  extract_bits_from_lwe_ciphertext                lwe_wopbs.rs (extract_bits, wop_pbs/mod.rs:66-225)
+  circuit_bootstrap_boolean                       wop_pbs/mod.rs:243-444
+  circuit_bootstrap_boolean_vertical_packing      wop_pbs/mod.rs:647-746
 
 Argument meaning and error behaviour follow the reference: output buffers are caller-owned and
 overwritten; dimension mismatches raise (the reference asserts, lwe_programmable_bootstrapping.rs
@@ -195,3 +200,102 @@ def vertical_packing(lut: np.ndarray, lwe_out: np.ndarray, ggsw_list: GgswCipher
     _check_engine(engine, ggsw_list)
     lwe_out[...] = engine.vertical_packing(ggsw_list.data.reshape(1, -1), ggsw_list.decomposition_base_log,
                                            ggsw_list.decomposition_level_count, lut).reshape(lwe_out.shape)
+
+
+class LwePrivateFunctionalPackingKeyswitchKeyList:
+    """The circuit bootstrap's private functional packing keyswitching keys
+    (entities/lwe_private_functional_packing_keyswitch_key_list.rs): data
+    [k+1 keys][input LweSize][level][(k+1)N], level l at index l-1, resident on the engine's GPU."""
+
+    def __init__(self, data, input_lwe_dimension: int, glwe_size: int, polynomial_size: int, base_log: int,
+                 level: int, engine: Engine):
+        self.input_key_lwe_dimension = input_lwe_dimension
+        self.glwe_size, self.output_polynomial_size = glwe_size, polynomial_size
+        self.decomposition_base_log, self.decomposition_level_count = base_log, level
+        words = glwe_size * (input_lwe_dimension + 1) * level * glwe_size * polynomial_size
+        d = np.ascontiguousarray(data, dtype=np.uint64)
+        if d.size != words:
+            raise ValueError(f"pfpksk list of {d.size} words, expected {words} ([k+1][LweSize][level][(k+1)N])")
+        p = engine.params
+        if (p.glwe_dimension + 1, p.polynomial_size) != (glwe_size, polynomial_size) or engine.big_dim != input_lwe_dimension:
+            raise ValueError("the engine's GlweSize / PolynomialSize / big LweDimension differ from the key list's")
+        self.engine = engine
+        engine.upload_pfpksk_list(d, base_log, level)
+
+    def __len__(self):
+        return self.glwe_size
+
+
+def private_functional_keyswitch_lwe_ciphertext_into_glwe_ciphertext(
+        pfpksk: LwePrivateFunctionalPackingKeyswitchKeyList, key_index: int, output_glwe: np.ndarray,
+        input_lwe: np.ndarray) -> None:
+    """output_glwe <- pfpks of input_lwe under key `key_index` of the list (reference order: key, output,
+    input; the reference takes one key of the list, the engine runs them all in one launch)."""
+    if input_lwe.shape[-1] != pfpksk.input_key_lwe_dimension + 1:
+        raise ValueError("Mismatched input LweDimension")
+    if output_glwe.shape[-1] != pfpksk.glwe_size * pfpksk.output_polynomial_size:
+        raise ValueError("Mismatched output GlweSize / PolynomialSize")
+    if not 0 <= key_index < len(pfpksk):
+        raise ValueError(f"key index {key_index} outside the list of {len(pfpksk)} keys")
+    out = pfpksk.engine.private_functional_packing_keyswitch(input_lwe)
+    output_glwe[...] = out[:, key_index].reshape(output_glwe.shape)
+
+
+def extract_bits_from_lwe_ciphertext(lwe_in: np.ndarray, lwe_list_out: np.ndarray,
+                                     fourier_bsk: FourierLweBootstrapKey, ksk: LweKeyswitchKey, delta_log: int,
+                                     number_of_bits_to_extract: int) -> None:
+    """lwe_list_out [nbits][n+1] <- the bits of lwe_in, most significant first (reference order)."""
+    eng = fourier_bsk.engine
+    if ksk.engine is not eng:
+        raise ValueError("the bootstrap key and the keyswitch key live on different engines")
+    if 64 < delta_log + number_of_bits_to_extract:
+        raise ValueError(f"Tried to extract {number_of_bits_to_extract} bits, while the maximum number of extractable "
+                         f"bits for delta_log {delta_log} is {64 - delta_log}")
+    if lwe_in.shape[-1] != eng.big_dim + 1:
+        raise ValueError(f"lwe_in needs to have an LWE dimension of {eng.big_dim}, got {lwe_in.shape[-1] - 1}")
+    if lwe_list_out.shape[-1] != eng.n + 1:
+        raise ValueError(f"lwe_list_out needs to have an LWE dimension of {eng.n}, got {lwe_list_out.shape[-1] - 1}")
+    if lwe_list_out.size // lwe_list_out.shape[-1] != number_of_bits_to_extract * (lwe_in.size // lwe_in.shape[-1]):
+        raise ValueError(f"lwe_list_out needs to have a ciphertext count of {number_of_bits_to_extract}")
+    lwe_list_out[...] = eng.extract_bits(lwe_in, delta_log, number_of_bits_to_extract).reshape(lwe_list_out.shape)
+
+
+def circuit_bootstrap_boolean(fourier_bsk: FourierLweBootstrapKey, lwe_in: np.ndarray, ggsw_out: GgswCiphertextList,
+                              delta_log: int, pfpksk_list: LwePrivateFunctionalPackingKeyswitchKeyList) -> None:
+    """ggsw_out <- GGSW encryptions of the bit at 2^delta_log of every lwe_in, with ggsw_out's
+    decomposition (reference order: bsk, lwe_in, ggsw_out, delta_log, pfpksk_list)."""
+    eng = fourier_bsk.engine
+    if pfpksk_list.engine is not eng:
+        raise ValueError("the bootstrap key and the pfpksk list live on different engines")
+    if lwe_in.shape[-1] != eng.n + 1:
+        raise ValueError(f"lwe_in needs to have an LWE dimension of {eng.n}, got {lwe_in.shape[-1] - 1}")
+    if (ggsw_out.glwe_size, ggsw_out.polynomial_size) != (pfpksk_list.glwe_size, pfpksk_list.output_polynomial_size):
+        raise ValueError("The output GGSW ciphertext needs the GlweSize and PolynomialSize of the pfpksks")
+    if len(ggsw_out) != lwe_in.size // lwe_in.shape[-1]:
+        raise ValueError(f"{len(ggsw_out)} output GGSWs for {lwe_in.size // lwe_in.shape[-1]} input ciphertexts")
+    ggsw_out.data[...] = eng.circuit_bootstrap(lwe_in, delta_log, ggsw_out.decomposition_base_log,
+                                               ggsw_out.decomposition_level_count).reshape(ggsw_out.data.shape)
+
+
+def circuit_bootstrap_boolean_vertical_packing(big_lut_as_polynomial_list: np.ndarray,
+                                               fourier_bsk: FourierLweBootstrapKey, lwe_list_out: np.ndarray,
+                                               lwe_list_in: np.ndarray,
+                                               pfpksk_list: LwePrivateFunctionalPackingKeyswitchKeyList,
+                                               level_cbs: int, base_log_cbs: int) -> None:
+    """lwe_list_out [nout][kN+1] <- the LUTs at the index whose bits lwe_list_in [nbits][n+1] encrypt at
+    q/2, most significant first; big_lut [nout * npoly][N] (reference order)."""
+    eng = fourier_bsk.engine
+    if pfpksk_list.engine is not eng:
+        raise ValueError("the bootstrap key and the pfpksk list live on different engines")
+    N = eng.params.polynomial_size
+    if big_lut_as_polynomial_list.ndim != 2 or big_lut_as_polynomial_list.shape[1] != N:
+        raise ValueError("big_lut must be [polynomial_count][PolynomialSize]")
+    if lwe_list_in.ndim != 2 or lwe_list_in.shape[1] != eng.n + 1:
+        raise ValueError(f"lwe_list_in needs to have an LWE dimension of {eng.n}")
+    if lwe_list_out.ndim != 2 or lwe_list_out.shape[1] != eng.big_dim + 1:
+        raise ValueError(f"lwe_list_out needs to have an LWE dimension of {eng.big_dim}")
+    nout, npolys = lwe_list_out.shape[0], big_lut_as_polynomial_list.shape[0]
+    if nout == 0 or npolys % nout:
+        raise ValueError(f"{npolys} LUT polynomials do not divide into {nout} outputs")
+    lut = big_lut_as_polynomial_list.reshape(1, nout, npolys // nout, N)
+    lwe_list_out[...] = eng.circuit_bootstrap_vertical_packing(lwe_list_in[None], base_log_cbs, level_cbs, lut)[0]

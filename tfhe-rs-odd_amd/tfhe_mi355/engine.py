@@ -422,6 +422,113 @@ class Engine:
                   L.shape[1], idxp, count, _ptr(out))
         return out
 
+    # -- WoP-PBS, the bootstrapped half: pfpks, bit extraction, circuit bootstrap -------------
+    def upload_pfpksk_list(self, pfpksk: np.ndarray, base_log: int, level: int) -> None:
+        """LwePrivateFunctionalPackingKeyswitchKeyList [k+1][kN+1][level][(k+1)N], level 1 first (the
+        reference's memory as it is); its decomposition belongs to the key."""
+        k = _u64(pfpksk)
+        _lib.call("tfhe_mi355_pfpksk_list_upload", self._h, _ptr(k), k.size, base_log, level)
+
+    def private_functional_packing_keyswitch(self, lwe_in) -> np.ndarray:
+        """private_functional_keyswitch_lwe_ciphertext_into_glwe_ciphertext under every key of the
+        list, batched: [count][kN+1] -> [count][k+1][(k+1)N]."""
+        x = _u64(lwe_in).reshape(-1, self.big_dim + 1)
+        out = np.empty((x.shape[0], self.params.glwe_dimension + 1, self.glwe_len), dtype=np.uint64)
+        _lib.call("tfhe_mi355_private_functional_packing_keyswitch", self._h, _ptr(x), _ptr(out), x.shape[0])
+        return out
+
+    def extract_bits(self, lwe_in, delta_log: int, nbits: int) -> np.ndarray:
+        """extract_bits (wop_pbs/mod.rs:66-225), batched: [count][kN+1] -> [count][nbits][n+1], most
+        significant bit first, each at q/2."""
+        if nbits <= 0 or delta_log < 0 or delta_log + nbits > 64 or (delta_log == 0 and nbits > 1):
+            raise ValueError(f"extract_bits: delta_log {delta_log}, nbits {nbits} out of range")
+        x = _u64(lwe_in).reshape(-1, self.big_dim + 1)
+        out = np.empty((x.shape[0], nbits, self.n + 1), dtype=np.uint64)
+        _lib.call("tfhe_mi355_extract_bits", self._h, _ptr(x), delta_log, nbits, _ptr(out), x.shape[0])
+        return out
+
+    def circuit_bootstrap(self, lwe_in, delta_log: int, cbs_base_log: int, cbs_level: int) -> np.ndarray:
+        """circuit_bootstrap_boolean (wop_pbs/mod.rs:243-444), batched: [count][n+1] ->
+        [count][cbs_level][k+1][(k+1)N] standard-domain GGSWs."""
+        if not 0 <= delta_log <= 63:
+            raise ValueError(f"circuit_bootstrap: delta_log {delta_log} out of range")
+        x = _u64(lwe_in).reshape(-1, self.n + 1)
+        out = np.empty((x.shape[0], cbs_level, self.params.glwe_dimension + 1, self.glwe_len), dtype=np.uint64)
+        _lib.call("tfhe_mi355_circuit_bootstrap", self._h, _ptr(x), delta_log, cbs_base_log, cbs_level, _ptr(out),
+                  x.shape[0])
+        return out
+
+    def _wop_luts(self, luts) -> np.ndarray:
+        N = self.params.polynomial_size
+        L = _u64(luts)
+        if L.ndim == 2:
+            L = L.reshape(1, 1, *L.shape)
+        elif L.ndim == 3:
+            L = L.reshape(1, *L.shape)
+        if L.ndim != 4 or L.shape[3] != N:
+            raise ValueError("luts must be [lut_count][nout][npoly][N]")
+        return L
+
+    def circuit_bootstrap_vertical_packing(self, lwe_in, cbs_base_log: int, cbs_level: int, luts,
+                                           lut_indexes=None) -> np.ndarray:
+        """circuit_bootstrap_boolean_vertical_packing (wop_pbs/mod.rs:647-746), batched: lwe_in
+        [count][nbits][n+1] (bits at q/2, most significant first), luts [lut_count][nout][npoly][N] (or
+        [nout][npoly][N], [npoly][N]); returns [count][nout][kN+1]."""
+        x = _u64(lwe_in)
+        if x.ndim != 3 or x.shape[2] != self.n + 1 or x.shape[1] == 0:
+            raise ValueError("circuit_bootstrap_vertical_packing: lwe_in must be [count][nbits][n+1]")
+        L = self._wop_luts(luts)
+        count, nbits = x.shape[0], x.shape[1]
+        idx, idxp = self._idx(lut_indexes, count, L.shape[0])
+        out = np.empty((count, L.shape[1], self.big_dim + 1), dtype=np.uint64)
+        _lib.call("tfhe_mi355_circuit_bootstrap_vertical_packing", self._h, _ptr(x), nbits, cbs_base_log, cbs_level,
+                  _ptr(L), L.shape[0], L.shape[1], L.shape[2], idxp, count, _ptr(out))
+        return out
+
+    def pfpks_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_private_functional_packing_keyswitch_scratch", count)
+
+    def extract_bits_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_extract_bits_scratch", count)
+
+    def circuit_bootstrap_scratch_bytes(self, cbs_level: int, count: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call("tfhe_mi355_circuit_bootstrap_scratch", self._h, cbs_level, count, ctypes.byref(b))
+        return b.value
+
+    def circuit_bootstrap_vertical_packing_scratch_bytes(self, nbits: int, cbs_level: int, lut_count: int, nout: int,
+                                                         npoly: int, count: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call("tfhe_mi355_circuit_bootstrap_vertical_packing_scratch", self._h, nbits, cbs_level, lut_count, nout,
+                  npoly, count, ctypes.byref(b))
+        return b.value
+
+    def private_functional_packing_keyswitch_async(self, d_in, d_out, count: int, stream=None, d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.pfpks_scratch_bytes(count), stream)
+        _lib.call("tfhe_mi355_private_functional_packing_keyswitch_async", self._h, _dev_ptr(d_in), _dev_ptr(d_out),
+                  count, sp, sb, _stream_ptr(stream))
+
+    def extract_bits_async(self, d_in, delta_log: int, nbits: int, d_out, count: int, stream=None,
+                           d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.extract_bits_scratch_bytes(count), stream)
+        _lib.call("tfhe_mi355_extract_bits_async", self._h, _dev_ptr(d_in), delta_log, nbits, _dev_ptr(d_out), count,
+                  sp, sb, _stream_ptr(stream))
+
+    def circuit_bootstrap_async(self, d_in, delta_log: int, cbs_base_log: int, cbs_level: int, d_ggsw_out, count: int,
+                                stream=None, d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.circuit_bootstrap_scratch_bytes(cbs_level, count), stream)
+        _lib.call("tfhe_mi355_circuit_bootstrap_async", self._h, _dev_ptr(d_in), delta_log, cbs_base_log, cbs_level,
+                  _dev_ptr(d_ggsw_out), count, sp, sb, _stream_ptr(stream))
+
+    def circuit_bootstrap_vertical_packing_async(self, d_in, nbits: int, cbs_base_log: int, cbs_level: int, d_luts,
+                                                 lut_count: int, nout: int, npoly: int, count: int, d_out,
+                                                 d_lut_indexes=None, stream=None, d_scratch=None) -> None:
+        need = self.circuit_bootstrap_vertical_packing_scratch_bytes(nbits, cbs_level, lut_count, nout, npoly, count)
+        sp, sb, _keep = self._scratch(d_scratch, need, stream)
+        _lib.call("tfhe_mi355_circuit_bootstrap_vertical_packing_async", self._h, _dev_ptr(d_in), nbits, cbs_base_log,
+                  cbs_level, _dev_ptr(d_luts), lut_count, nout, npoly, _dev_ptr(d_lut_indexes), count, _dev_ptr(d_out),
+                  sp, sb, _stream_ptr(stream))
+
     # -- device (torch) async ops -------------------------------------------------------
     # Every device scratch the C ABI needs comes from the caller (include/tfhe_mi355.h): pass
     # d_scratch (>= the matching *_scratch_bytes), or let these wrappers allocate it from torch's

@@ -248,3 +248,39 @@ ALL = {p.name: p for p in [PARAM_MESSAGE_2_CARRY_2_KS_PBS, PARAM_MESSAGE_4_CARRY
                            PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_2_KS_PBS, MANTICORE_PARAMETERS] + GADGET_ALL}
 ALL.update(SHORTINT_ALL)
 ALL.update(MULTI_BIT_ALL)
+
+
+@dataclass(frozen=True)
+class WopbsParameters(ClassicPBSParameters):
+    """Mirror of shortint WopbsParameters (shortint/parameters/mod.rs): the classic fields plus the
+    private functional packing keyswitch and circuit bootstrap decompositions.  Usable wherever a
+    ClassicPBSParameters creates a context."""
+
+    pfks_base_log: int = 0
+    pfks_level: int = 0
+    pfks_modular_std_dev: float = 0.0
+    cbs_base_log: int = 0
+    cbs_level: int = 0
+
+
+# shortint/parameters/parameters_wopbs_message_carry.rs:272-291, 292-311, 432-451
+WOPBS_PARAM_MESSAGE_1_CARRY_1_KS_PBS = WopbsParameters(
+    lwe_dimension=653, glwe_dimension=1, polynomial_size=2048,
+    lwe_modular_std_dev=0.00003604499526942373, glwe_modular_std_dev=0.00000000000000029403601535432533,
+    pbs_base_log=15, pbs_level=2, ks_base_log=5, ks_level=2, message_modulus=2, carry_modulus=2,
+    pfks_base_log=15, pfks_level=2, pfks_modular_std_dev=0.00000000000000029403601535432533,
+    cbs_base_log=5, cbs_level=3, name="WOPBS_PARAM_MESSAGE_1_CARRY_1_KS_PBS")
+WOPBS_PARAM_MESSAGE_1_CARRY_2_KS_PBS = WopbsParameters(
+    lwe_dimension=487, glwe_dimension=3, polynomial_size=512,
+    lwe_modular_std_dev=0.00054842163045222410337, glwe_modular_std_dev=0.000000000002573000821792597679153983627,
+    pbs_base_log=9, pbs_level=3, ks_base_log=2, ks_level=4, message_modulus=2, carry_modulus=4,
+    pfks_base_log=9, pfks_level=3, pfks_modular_std_dev=0.000000000002573000821792597679153983627,
+    cbs_base_log=3, cbs_level=5, name="WOPBS_PARAM_MESSAGE_1_CARRY_2_KS_PBS")
+WOPBS_PARAM_MESSAGE_2_CARRY_2_KS_PBS = WopbsParameters(
+    lwe_dimension=769, glwe_dimension=1, polynomial_size=2048,
+    lwe_modular_std_dev=0.0000043131554647504185, glwe_modular_std_dev=0.00000000000000029403601535432533,
+    pbs_base_log=15, pbs_level=2, ks_base_log=6, ks_level=2, message_modulus=4, carry_modulus=4,
+    pfks_base_log=15, pfks_level=2, pfks_modular_std_dev=0.00000000000000029403601535432533,
+    cbs_base_log=5, cbs_level=3, name="WOPBS_PARAM_MESSAGE_2_CARRY_2_KS_PBS")
+WOPBS_ALL = {p.name: p for p in [WOPBS_PARAM_MESSAGE_1_CARRY_1_KS_PBS, WOPBS_PARAM_MESSAGE_1_CARRY_2_KS_PBS,
+                                 WOPBS_PARAM_MESSAGE_2_CARRY_2_KS_PBS]}

@@ -9,6 +9,10 @@
   ServerKey.programmable_bootstrap_keyswitch_assign         server_key/mod.rs:859-932
   ServerKey.trivial_pbs_assign                              server_key/mod.rs:763-781
   gen_keys                                                  shortint/mod.rs (gen_keys)
+  ClientKey.encrypt_without_padding / decrypt_without_padding
+                                                            engine/client_side.rs:273-317, client_key/mod.rs:424-483
+  WopbsKey.new_wopbs_key_only_for_wopbs / generate_lut[_without_padding] / wopbs /
+  programmable_bootstrapping_without_padding                wopbs/mod.rs:235-495, 825-857
 
 Batched forms (`apply_lookup_table_batch`) hand a whole layer of independent ciphertexts to the
 GPU in one launch -- the shape the integer layer produces (radix_parallel/mul.rs:347-407).
@@ -22,7 +26,7 @@ import numpy as np
 
 from . import client
 from .engine import Engine, fill_accumulator
-from .parameters import ClassicPBSParameters
+from .parameters import ClassicPBSParameters, WopbsParameters
 
 NOISE_ZERO = 0
 NOISE_NOMINAL = 1
@@ -105,6 +109,30 @@ class ClientKey:
 
     def decrypt(self, ct: Ciphertext) -> int:
         return self.decrypt_message_and_carry(ct) % ct.message_modulus
+
+    # -- without padding bit (the WoP-PBS encoding): delta doubled, the message not reduced --------
+    def encrypt_without_padding_many(self, messages) -> list[Ciphertext]:
+        p = self.parameters
+        m = np.asarray(messages, dtype=np.uint64)
+        key, std = self._enc_key()
+        self._enc_counter += 1
+        cts = client.lwe_encrypt((self.seed << 20) + self._enc_counter, key, m * np.uint64(2 * p.delta), std)
+        return [Ciphertext(cts[i].copy(), p.message_modulus - 1, NOISE_NOMINAL, p.message_modulus,
+                           p.carry_modulus, self.pbs_order) for i in range(len(m))]
+
+    def encrypt_without_padding(self, message: int) -> Ciphertext:
+        return self.encrypt_without_padding_many([message])[0]
+
+    def decrypt_message_and_carry_without_padding_many(self, cts: list[Ciphertext]) -> np.ndarray:
+        key = self.large_lwe_secret_key if cts[0].pbs_order == KEYSWITCH_BOOTSTRAP else self.small_lwe_secret_key
+        raw = client.lwe_decrypt(key, np.stack([c.ct for c in cts]))
+        return client.decode(raw, 2 * self.parameters.delta)
+
+    def decrypt_message_and_carry_without_padding(self, ct: Ciphertext) -> int:
+        return int(self.decrypt_message_and_carry_without_padding_many([ct])[0])
+
+    def decrypt_without_padding(self, ct: Ciphertext) -> int:
+        return self.decrypt_message_and_carry_without_padding(ct) % ct.message_modulus
 
 
 class ServerKey:
@@ -253,6 +281,79 @@ class ServerKey:
     def carry_extract(self, ct: Ciphertext) -> Ciphertext:
         acc = self.generate_lookup_table(lambda x: x // ct.message_modulus)
         return self.apply_lookup_table(ct, acc)
+
+
+class WopbsKey:
+    """shortint WopbsKey (wopbs/mod.rs) on the engine of its server key: the circuit bootstrap's private
+    functional packing keyswitching keys next to the bootstrapping and keyswitching keys."""
+
+    def __init__(self, wopbs_server_key: ServerKey, param: WopbsParameters, pfpksk: np.ndarray | None = None):
+        if not isinstance(param, WopbsParameters):
+            raise ValueError("WopbsKey needs WopbsParameters")
+        if param.pbs_level > 4:
+            raise ValueError(f"pbs_level {param.pbs_level}: no classic PBS kernel for WoP-PBS sets of 5 or 6 levels")
+        self.wopbs_server_key = wopbs_server_key
+        self.param = param
+        if pfpksk is not None:
+            wopbs_server_key.engine.upload_pfpksk_list(pfpksk, param.pfks_base_log, param.pfks_level)
+
+    @classmethod
+    def new_wopbs_key_only_for_wopbs(cls, cks: ClientKey, sks: ServerKey) -> "WopbsKey":
+        p = cks.parameters
+        if not isinstance(p, WopbsParameters):
+            raise ValueError("new_wopbs_key_only_for_wopbs: the client key's parameters are no WopbsParameters")
+        pfpksk = client.gen_pfpksk_list(cks.seed * 7 + 5, cks.large_lwe_secret_key, cks.glwe_secret_key,
+                                        p.glwe_dimension, p.polynomial_size, p.pfks_base_log, p.pfks_level,
+                                        p.pfks_modular_std_dev)
+        return cls(sks, p, pfpksk)
+
+    @property
+    def engine(self) -> Engine:
+        return self.wopbs_server_key.engine
+
+    def _basis_bits(self, ct: Ciphertext) -> int:
+        return int(np.ceil(np.log2(ct.message_modulus * ct.carry_modulus)))
+
+    def _lut(self, ct: Ciphertext, f, delta_log: int) -> np.ndarray:
+        lut = np.zeros(self.param.polynomial_size, dtype=np.uint64)
+        for i in range(ct.message_modulus * ct.carry_modulus):
+            lut[i] = np.uint64((int(f(i % ct.message_modulus)) << delta_log) % (1 << 64))
+        return lut
+
+    def generate_lut(self, ct: Ciphertext, f) -> np.ndarray:
+        """one bit of padding: entry i = f(i mod message_modulus) << (63 - log2(basis))."""
+        return self._lut(ct, f, 64 - self._basis_bits(ct) - 1)
+
+    def generate_lut_without_padding(self, ct: Ciphertext, f) -> np.ndarray:
+        return self._lut(ct, f, 64 - self._basis_bits(ct))
+
+    def extract_bits_circuit_bootstrapping(self, cts, lut, delta_log: int, nbits: int):
+        """extract_bits then circuit_bootstrap_boolean_vertical_packing (wopbs/mod.rs:825-857); a list of
+        ciphertexts is one batch."""
+        single = isinstance(cts, Ciphertext)
+        batch = [cts] if single else list(cts)
+        if batch[0].pbs_order != KEYSWITCH_BOOTSTRAP:
+            raise ValueError("WoP-PBS runs on big-key ciphertexts (KeyswitchBootstrap order)")
+        p = self.param
+        lut = np.ascontiguousarray(lut, dtype=np.uint64).reshape(1, 1, -1, p.polynomial_size)
+        bits = self.engine.extract_bits(np.stack([c.ct for c in batch]), delta_log, nbits)
+        out = self.engine.circuit_bootstrap_vertical_packing(bits, p.cbs_base_log, p.cbs_level, lut)
+        sks = self.wopbs_server_key
+        res = [Ciphertext(out[i, 0].copy(), sks.message_modulus - 1, NOISE_NOMINAL, sks.message_modulus,
+                          sks.carry_modulus, batch[i].pbs_order) for i in range(len(batch))]
+        return res[0] if single else res
+
+    def wopbs(self, ct_in, lut):
+        p = self.param
+        delta_log = p.delta.bit_length() - 1
+        return self.extract_bits_circuit_bootstrapping(ct_in, lut, delta_log,
+                                                       int(np.log2(p.message_modulus * p.carry_modulus)))
+
+    def programmable_bootstrapping_without_padding(self, ct_in, lut):
+        p = self.param
+        delta_log = (2 * p.delta).bit_length() - 1
+        return self.extract_bits_circuit_bootstrapping(ct_in, lut, delta_log,
+                                                       int(np.log2(p.message_modulus * p.carry_modulus)))
 
 
 class CompressedServerKey:
