@@ -1,7 +1,7 @@
 """GPU parity of the gadget layer's kernels against the oracle.
 
 Bar: bit-exact u64 outputs for the blind rotation without sample extraction, the LWE -> GLWE
-packing keyswitch (MFMA and scalar kernels), the GLWE x polynomial products, and the complete
+packing keyswitch (the MFMA kernel; the scalar one in test_keyswitch_gpu.py), the GLWE x polynomial products, and the complete
 gadget evaluations (apply_lut, BPR24 gadget, MVB, depth-2 tree bootstrapping) run once on the
 engine and once on OracleEngine from the same client key.
 """
@@ -40,18 +40,19 @@ def test_blind_rotate_bit_exact(orc, which, request):
     assert np.array_equal(ext, pbs)
 
 
-@pytest.mark.parametrize("mfma", [True, False])
-def test_packing_keyswitch_bit_exact(orc, keys_manticore, mfma, monkeypatch):
+@pytest.mark.parametrize("mfma", [True])
+def test_packing_keyswitch_bit_exact(orc, keys_manticore, mfma):
+    """The MFMA kernel.  The library reads TFHE_MI355_KS_NO_MFMA once per process, so the scalar kernel
+    runs on the same key and rows in a fresh process (test_keyswitch_gpu.py, the `scalar` child)."""
     from tfhe_mi355 import Engine
 
     p = keys_manticore.params
     k, N = p.glwe_dimension, p.polynomial_size
-    if not mfma:
-        monkeypatch.setenv("TFHE_MI355_KS_NO_MFMA", "1")
     eng = Engine(p, 0)
     pksk = orc.gen_pksk(31, keys_manticore.glwe_sk, keys_manticore.glwe_sk, k, N, p.ks_base_log, p.ks_level,
                         p.glwe_modular_std_dev)
     eng.upload_packing_keyswitch_key(pksk, p.ks_base_log, p.ks_level)
+    assert eng.pks_scratch_bytes(1) > 0  # 0 exactly when the scalar kernel is chosen
     rng = np.random.default_rng(5)
     x = rng.integers(0, 2 ** 64, (67, k * N + 1), dtype=np.uint64)
     x[3] = 0
