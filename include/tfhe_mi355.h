@@ -155,7 +155,8 @@ int tfhe_mi355_host_free(void *ptr);
 /* Create / destroy an engine context on `device`.
  * Accepted decompositions: 2 <= pbs_base_log and pbs_base_log * pbs_level <= 30 for N <= 2048 and
  * multi-bit; <= 63 for classic N >= 4096, with pbs_base_log <= 15 when pbs_level > 1 (the split
- * CMUX packs signed digits into int16).  Every reference parameter set is inside these bounds.
+ * CMUX packs signed digits into int16) and pbs_base_log <= 31 when pbs_level = 1 (it computes them
+ * as int32).  Every reference parameter set is inside these bounds.
  * Replaces Fft::new + the shortint engine's thread-local buffers
  * (fft64/math/fft/mod.rs:146-193, shortint/engine/mod.rs:23-70,163-235). */
 int tfhe_mi355_context_create(const TfheMi355Parameters *params, int device,

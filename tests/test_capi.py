@@ -135,6 +135,9 @@ def test_unsupported_multi_bit_parameters_are_rejected():
     (32768, 16, 2, False),   # grouped N = 32768 path: 32-bit decomposition needs beta * L <= 30
     (32768, 11, 3, True),    # PARAM_MESSAGE_1_CARRY_7 (64-bit decomposition, 33 bits)
     (4096, 22, 1, True),     # one level: no packing
+    (4096, 31, 1, True),     # one level: the widest digit an int32 holds, +2^30
+    (8192, 32, 1, False),    # a digit of +2^31 would wrap in int32
+    (16384, 63, 1, False),
 ])
 def test_context_create_validates_split_decomposition(N, base_log, level, ok):
     """tfhe_mi355_context_create checks the decomposition before touching the GPU (capi.cpp):

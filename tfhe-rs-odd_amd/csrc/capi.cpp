@@ -1896,6 +1896,11 @@ void validate_parameters(const TfheMi355Parameters &p) {
     if (split && p.pbs_level > 1 && p.pbs_base_log > 15)
         fail("pbs base_log %u > 15 with %u levels at N = %u (digits are packed as int16)", p.pbs_base_log,
              p.pbs_level, p.polynomial_size);
+    // ... and returns every digit as int32 (decompose64): the one-level digit lies in
+    // (-2^(beta-1), 2^(beta-1)], so beta <= 31 (beta = 32 would wrap +2^31 to -2^31)
+    if (split && p.pbs_level == 1 && p.pbs_base_log > 31)
+        fail("pbs base_log %u > 31 with one level at N = %u (digits are computed as int32)", p.pbs_base_log,
+             p.polynomial_size);
     if (p.ks_level && (p.ks_base_log == 0 || p.ks_base_log * p.ks_level >= 64)) fail("invalid ks decomposition");
     if (p.lwe_dimension == 0) fail("lwe_dimension must be > 0");
 }
