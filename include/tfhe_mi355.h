@@ -16,7 +16,9 @@
  *       standard BSK     = [n][L][k+1 rows][k+1 polys][N]          (ggsw_ciphertext.rs:185-216)
  *       multi-bit BSK    = [n/g][2^g][L][k+1][k+1][N]              (lwe_multi_bit_bootstrap_key.rs)
  *       KSK              = [in_dim][L_ks][out_dim+1], levels stored L..1
- *                          (lwe_keyswitch_key.rs:102-108, lwe_keyswitch_key_generation.rs:109);
+ *                          (lwe_keyswitch_key.rs:102-108, lwe_keyswitch_key_generation.rs:109)
+ *       relin. key       = [k(k+1)/2][L][k+1 polys][N], level L first
+ *                          (custom_glwe_relinearization_key.rs, custom_relinearization_key_generation.rs:134-138);
  *   - "_async" entry points take DEVICE pointers and a hipStream_t (as void*), enqueue the work
  *     and return immediately; the others take HOST pointers and return after the outputs are
  *     written (synchronous).  The host-pointer forms pipeline the batch in chunks through
@@ -354,6 +356,35 @@ int tfhe_mi355_glwe_poly_mul_async(TfheMi355Context *ctx, const uint64_t *d_glwe
                                    const uint64_t *d_polys, size_t npoly, size_t count, int extract,
                                    uint64_t *d_out, void *stream);
 
+/* GLWE x GLWE product with relinearisation, the fork's "even transistor" multiplication (glwe_mult,
+ * core_crypto/algorithms/custom_glwe_glwe_product.rs:13-321; lwe_mult, gadget/engine/mod.rs:680-751).
+ * Relinearisation key layout [k(k+1)/2][level][(k+1)*N] (entities/custom_glwe_relinearization_key.rs):
+ * block n = i(i+1)/2 + j (j <= i) holds `level` GLWE encryptions, level L first, of the polynomial
+ * (S_i * S_j) << (64 - base_log*lvl) under the GLWE key (custom_relinearization_key_generation.rs:
+ * 72-161); its decomposition belongs to the key, 1 <= base_log <= 31, base_log*level <= 63.  On a
+ * multi-device context the key goes to every device.
+ * glwe_mult: both GLWEs are shifted right by 32 - log_p/2 (log_p even, <= 64), tensored and
+ * relinearised: glwe_lhs, glwe_rhs count x (k+1)*N -> out count x (k+1)*N, or count x (k*N+1) when
+ * extract != 0 (the degree-0 sample of the product).  lwe_mult: both LWEs (under the big key) are packed
+ * by the packing keyswitch (one launch over the 2*count rows; its key must be uploaded too), multiplied
+ * and sample-extracted: count x (k*N+1) each.  N a power of two in [256, 2048], 1 <= k <= 5,
+ * (k+1)*N <= 4096; anything else fails, as do an odd log_p, a missing key and an `out` that overlaps
+ * an input.  The _scratch queries fail until the key(s) are uploaded. */
+int tfhe_mi355_relinearization_key_upload(TfheMi355Context *ctx, const uint64_t *rlk, size_t len, uint32_t base_log,
+                                          uint32_t level);
+int tfhe_mi355_glwe_mult(TfheMi355Context *ctx, const uint64_t *glwe_lhs, const uint64_t *glwe_rhs, uint32_t log_p,
+                         int extract, uint64_t *out, size_t count);
+int tfhe_mi355_glwe_mult_async(TfheMi355Context *ctx, const uint64_t *d_glwe_lhs, const uint64_t *d_glwe_rhs,
+                               uint32_t log_p, int extract, uint64_t *d_out, size_t count, void *d_scratch,
+                               size_t scratch_bytes, void *stream);
+int tfhe_mi355_glwe_mult_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+int tfhe_mi355_lwe_mult(TfheMi355Context *ctx, const uint64_t *lwe_lhs, const uint64_t *lwe_rhs, uint32_t log_p,
+                        uint64_t *lwe_out, size_t count);
+int tfhe_mi355_lwe_mult_async(TfheMi355Context *ctx, const uint64_t *d_lwe_lhs, const uint64_t *d_lwe_rhs,
+                              uint32_t log_p, uint64_t *d_lwe_out, size_t count, void *d_scratch,
+                              size_t scratch_bytes, void *stream);
+int tfhe_mi355_lwe_mult_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+
 /* GGSW x GLWE operations on GGSW ciphertexts that are data, not the context's key: every item of a
  * batch brings its own, and the decomposition (base_log, level; base_log * level <= 32) is an
  * argument of the call -- the circuit-bootstrap decomposition of WoP-PBS, not the PBS one.  N in
@@ -558,6 +589,10 @@ int tfhe_mi355_client_gen_packing_keyswitch_key(uint64_t seed, const uint64_t *i
                                                 const uint64_t *glwe_sk, uint32_t k, uint32_t N,
                                                 uint32_t base_log, uint32_t level, double std_dev,
                                                 uint64_t *pksk, uint32_t threads);
+/* relinearisation key [k(k+1)/2][level][(k+1)N], level L first (custom_relinearization_key_generation.rs:72-161):
+ * block n = i(i+1)/2 + j (j <= i), level lvl encrypts (S_i * S_j) << (64 - base_log*lvl) under glwe_sk */
+int tfhe_mi355_client_gen_relinearization_key(uint64_t seed, const uint64_t *glwe_sk, uint32_t k, uint32_t N,
+                                              uint32_t base_log, uint32_t level, double std_dev, uint64_t *rlk);
 /* pfpksk list of the circuit bootstrap [k+1][in_dim+1][level][(k+1)N], level 1 first (lwe_wopbs.rs:80-158):
  * key g, block i, level lvl encrypts -s_i * P_g * 2^(64 - base_log*lvl); s_(in_dim) = -1 (the body),
  * P_g = polynomial g of the GLWE key (g < k) or the constant -1 (g = k) */

@@ -256,6 +256,10 @@ struct TfheMi355Context {
     DeviceBuffer pfpksk, pfpksk_planes;
     uint32_t pfks_base_log = 0, pfks_level = 0;
     bool pfpksk_ready = false, pfpksk_planes_ready = false;
+    // GLWE relinearisation key of the gadget layer's lwe_mult (glwe_mult.hip), the reference's order
+    DeviceBuffer rlk;
+    uint32_t rlk_base_log = 0, rlk_level = 0;
+    bool rlk_ready = false;
     KernelTimer timer;  // per-kernel durations (tfhe_mi355_kernel_timing_*), off by default
     // one u32 the quad CMUX sets when a flag wait timed out (check_quad_fail); allocated zeroed at
     // creation for the contexts that can take the quad path (quad_max > 0)
@@ -307,6 +311,7 @@ struct TfheMi355Context {
     size_t ksk_len() const { return big_dim() * p.ks_level * (n() + 1); }
     size_t pksk_len(uint32_t level) const { return big_dim() * level * glwe_len(); }
     size_t pfpksk_len(uint32_t level) const { return (k() + 1) * (big_dim() + 1) * level * glwe_len(); }
+    size_t rlk_len(uint32_t level) const { return k() * (k() + 1) / 2 * level * glwe_len(); }
 };
 
 namespace {
@@ -747,6 +752,117 @@ void launch_glwe_poly_mul_dev(TfheMi355Context *c, const uint64_t *d_glwe, size_
 }
 
 // ---- GGSW operations (ggsw_ops.hip): per-item GGSW ciphertexts, decomposition chosen per call ----
+// ---- GLWE x GLWE product with relinearisation (glwe_mult.hip) -----------------------------------
+void require_rlk(const TfheMi355Context *c) {
+    if (!c->rlk_ready) fail("relinearization key not uploaded");
+}
+
+void require_glwe_mult_shape(const TfheMi355Context *c) {
+    if (!glwe_mult_supported((int)c->N(), (int)c->k()))
+        fail("glwe_mult: N must be a power of two in [256, 2048], 1 <= k <= 5 and (k+1)*N <= 4096 (got N=%zu k=%zu)",
+             c->N(), c->k());
+}
+
+void validate_log_p(uint32_t log_p) {
+    if (log_p > 64) fail("glwe_mult: log_p %u > 64", log_p);
+    if (log_p & 1) fail("glwe_mult: log_p %u is odd (the reference asserts an even one)", log_p);
+}
+
+// [a, a + an) and [b, b + bn) (u64 words) share a word
+bool words_overlap(const uint64_t *a, size_t an, const uint64_t *b, size_t bn) {
+    return an && bn && a < b + bn && b < a + an;
+}
+
+size_t glwe_mult_scratch(const TfheMi355Context *c, size_t count) {
+    return align256(glwe_mult_scratch_bytes((int)c->N(), (int)c->k(), count));
+}
+
+void launch_glwe_mult_dev(TfheMi355Context *c, const uint64_t *d_lhs, const uint64_t *d_rhs, uint32_t log_p,
+                          bool extract, uint64_t *d_out, size_t count, void *scratch, size_t scratch_bytes,
+                          hipStream_t s) {
+    require_glwe_mult_shape(c);
+    validate_log_p(log_p);
+    require_rlk(c);
+    if (count == 0) return;
+    if (count > 0x7fffffffu) fail("count too large");
+    const size_t out_words = extract ? c->big_dim() + 1 : c->glwe_len();
+    if (words_overlap(d_out, count * out_words, d_lhs, count * c->glwe_len()) ||
+        words_overlap(d_out, count * out_words, d_rhs, count * c->glwe_len()))
+        fail("glwe_mult: out overlaps an input");
+    require_scratch(scratch ? scratch_bytes : 0, glwe_mult_scratch(c, count));
+    GlweMultLaunch a;
+    a.lhs = d_lhs;
+    a.rhs = d_rhs;
+    a.out = d_out;
+    a.tr = reinterpret_cast<uint64_t *>(scratch);
+    a.rlk = reinterpret_cast<const uint64_t *>(c->rlk.ptr);
+    a.k = (int)c->k();
+    a.N = (int)c->N();
+    a.log_p = (int)log_p;
+    a.base_log = (int)c->rlk_base_log;
+    a.level = (int)c->rlk_level;
+    a.extract = extract ? 1 : 0;
+    a.count = count;
+    a.timer = c->timer_or_null();
+    check(launch_glwe_mult(a, s), "launch glwe_mult");
+}
+
+// lwe_mult: scratch = [2 count LWE rows, lhs then rhs | their packed GLWEs | packing-KS digits, then
+// (reused in stream order) the product's T/R polynomials]
+size_t lwe_mult_scratch(const TfheMi355Context *c, size_t count) {
+    return align256(2 * count * (c->big_dim() + 1) * 8) + align256(2 * count * c->glwe_len() * 8) +
+           std::max(align256(pks_scratch_bytes(c, 2 * count)), glwe_mult_scratch(c, count));
+}
+
+void launch_lwe_mult_dev(TfheMi355Context *c, const uint64_t *d_lhs, const uint64_t *d_rhs, uint32_t log_p,
+                         uint64_t *d_out, size_t count, void *scratch, size_t scratch_bytes, hipStream_t s) {
+    require_glwe_mult_shape(c);
+    validate_log_p(log_p);
+    require_rlk(c);
+    if (!c->pksk_ready) fail("packing keyswitching key not uploaded");
+    if (count == 0) return;
+    if (count > 0x3fffffffu) fail("count too large");
+    const size_t lwe = c->big_dim() + 1, glwe = c->glwe_len();
+    if (words_overlap(d_out, count * lwe, d_lhs, count * lwe) || words_overlap(d_out, count * lwe, d_rhs, count * lwe))
+        fail("lwe_mult: out overlaps an input");
+    require_scratch(scratch ? scratch_bytes : 0, lwe_mult_scratch(c, count));
+    char *p = reinterpret_cast<char *>(scratch);
+    uint64_t *rows = reinterpret_cast<uint64_t *>(p);
+    p += align256(2 * count * lwe * 8);
+    uint64_t *packed = reinterpret_cast<uint64_t *>(p);
+    p += align256(2 * count * glwe * 8);
+    const size_t rest = scratch_bytes - (size_t)(p - reinterpret_cast<char *>(scratch));
+    check(hipMemcpyAsync(rows, d_lhs, count * lwe * 8, hipMemcpyDeviceToDevice, s), "gather lhs");
+    check(hipMemcpyAsync(rows + count * lwe, d_rhs, count * lwe * 8, hipMemcpyDeviceToDevice, s), "gather rhs");
+    {
+        TimedLaunch tl(c->timer_or_null(), "packing_keyswitch", s);
+        launch_packing_ks_dev(c, rows, packed, 2 * count, p, rest, s);
+    }
+    launch_glwe_mult_dev(c, packed, packed + count * glwe, log_p, true, d_out, count, p, rest, s);
+}
+
+// host-pointer form of a two-input product: pairs in chunks through device buffers of the call's own,
+// on the context's stream; f(d_lhs, d_rhs, d_out, n, d_scratch, scratch_bytes, stream) launches one chunk
+template <class Scratch, class F>
+void host_pair_call(TfheMi355Context *ctx, const uint64_t *lhs, const uint64_t *rhs, size_t in_words, uint64_t *out,
+                    size_t out_words, size_t count, Scratch &&scratch_bytes, F &&f) {
+    if (count == 0) return;
+    const size_t chunk = std::min<size_t>(count, 4096);
+    DeviceBuffer d_lhs, d_rhs, d_out, d_scr;
+    d_lhs.reserve(chunk * in_words * 8);
+    d_rhs.reserve(chunk * in_words * 8);
+    d_out.reserve(chunk * out_words * 8);
+    d_scr.reserve(std::max<size_t>(scratch_bytes(chunk), 256));
+    hipStream_t s = ctx->stream;
+    for (size_t a = 0; a < count; a += chunk) {
+        const size_t n = std::min(chunk, count - a);
+        check(hipMemcpyAsync(d_lhs.ptr, lhs + a * in_words, n * in_words * 8, hipMemcpyHostToDevice, s), "H2D lhs");
+        check(hipMemcpyAsync(d_rhs.ptr, rhs + a * in_words, n * in_words * 8, hipMemcpyHostToDevice, s), "H2D rhs");
+        f((const uint64_t *)d_lhs.ptr, (const uint64_t *)d_rhs.ptr, (uint64_t *)d_out.ptr, n, d_scr.ptr, d_scr.bytes, s);
+        check(hipMemcpyAsync(out + a * out_words, d_out.ptr, n * out_words * 8, hipMemcpyDeviceToHost, s), "D2H out");
+        check(hipStreamSynchronize(s), "product sync");
+    }
+}
 size_t ggsw_polys(const TfheMi355Context *c, uint32_t level) { return (size_t)level * (c->k() + 1) * (c->k() + 1); }
 size_t ggsw_std_words(const TfheMi355Context *c, uint32_t level) { return ggsw_polys(c, level) * c->N(); }
 size_t ggsw_fourier_bytes(const TfheMi355Context *c, uint32_t level) {
@@ -2684,6 +2800,131 @@ int tfhe_mi355_packing_keyswitch_async(TfheMi355Context *ctx, const uint64_t *d_
         if (!ctx || (!d_lwe_in && count) || (!d_glwe_out && count)) fail("null argument");
         check(hipSetDevice(ctx->device), "hipSetDevice");
         launch_packing_ks_dev(ctx, d_lwe_in, d_glwe_out, count, d_scratch, scratch_bytes, (hipStream_t)stream);
+    });
+}
+
+int tfhe_mi355_relinearization_key_upload(TfheMi355Context *ctx, const uint64_t *rlk, size_t len, uint32_t base_log,
+                                          uint32_t level) {
+    return guarded([&] {
+        if (!ctx || !rlk) fail("null argument");
+        if (level == 0 || base_log == 0 || base_log > 31 || (uint64_t)base_log * level > 63)
+            fail("invalid relinearization decomposition %u x %u (1 <= base_log <= 31, base_log*level <= 63)", base_log,
+                 level);
+        if (ctx->multi()) {  // a gadget-layer key: uploaded to every device from the host
+            auto w = key_write_all(ctx);
+            for (auto *s : ctx->shards) abi(tfhe_mi355_relinearization_key_upload(s, rlk, len, base_log, level));
+            return;
+        }
+        KeyWrite kw(ctx);
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        require_glwe_mult_shape(ctx);
+        if (len != ctx->rlk_len(level))
+            fail("relinearization key has %zu words, expected %zu ([k(k+1)/2][level][(k+1)N])", len, ctx->rlk_len(level));
+        ctx->rlk_ready = false;
+        ctx->rlk.reserve(len * sizeof(uint64_t));
+        check(hipMemcpy(ctx->rlk.ptr, rlk, len * sizeof(uint64_t), hipMemcpyHostToDevice), "upload rlk");
+        ctx->rlk_base_log = base_log;
+        ctx->rlk_level = level;
+        ctx->rlk_ready = true;
+    });
+}
+
+int tfhe_mi355_glwe_mult(TfheMi355Context *ctx, const uint64_t *glwe_lhs, const uint64_t *glwe_rhs, uint32_t log_p,
+                         int extract, uint64_t *out, size_t count) {
+    return guarded([&] {
+        if (!ctx || (!glwe_lhs && count) || (!glwe_rhs && count) || (!out && count)) fail("null argument");
+        const size_t glwe = ctx->glwe_len(), out_words = extract ? ctx->big_dim() + 1 : glwe;
+        if (words_overlap(out, count * out_words, glwe_lhs, count * glwe) ||
+            words_overlap(out, count * out_words, glwe_rhs, count * glwe))
+            fail("glwe_mult: out overlaps an input");
+        if (ctx->multi())
+            return split_rows(ctx, count, [&](TfheMi355Context *s, size_t a, size_t n) {
+                return tfhe_mi355_glwe_mult(s, glwe_lhs + a * glwe, glwe_rhs + a * glwe, log_p, extract,
+                                            out + a * out_words, n);
+            });
+        std::lock_guard<std::mutex> g(ctx->mu);
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        require_glwe_mult_shape(ctx);
+        validate_log_p(log_p);
+        require_rlk(ctx);
+        host_pair_call(
+            ctx, glwe_lhs, glwe_rhs, glwe, out, out_words, count, [&](size_t n) { return glwe_mult_scratch(ctx, n); },
+            [&](const uint64_t *l, const uint64_t *r, uint64_t *o, size_t n, void *sc, size_t sb, hipStream_t s) {
+                launch_glwe_mult_dev(ctx, l, r, log_p, extract != 0, o, n, sc, sb, s);
+            });
+    });
+}
+
+int tfhe_mi355_glwe_mult_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || !bytes) fail("null argument");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        require_glwe_mult_shape(ctx);
+        if (!ctx->rlk_ready) fail("relinearization key not uploaded: the scratch is defined from its upload on");
+        *bytes = glwe_mult_scratch(ctx, count);
+    });
+}
+
+int tfhe_mi355_glwe_mult_async(TfheMi355Context *ctx, const uint64_t *d_glwe_lhs, const uint64_t *d_glwe_rhs,
+                               uint32_t log_p, int extract, uint64_t *d_out, size_t count, void *d_scratch,
+                               size_t scratch_bytes, void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!d_glwe_lhs && count) || (!d_glwe_rhs && count) || (!d_out && count)) fail("null argument");
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        launch_glwe_mult_dev(ctx, d_glwe_lhs, d_glwe_rhs, log_p, extract != 0, d_out, count, d_scratch, scratch_bytes,
+                             (hipStream_t)stream);
+    });
+}
+
+int tfhe_mi355_lwe_mult(TfheMi355Context *ctx, const uint64_t *lwe_lhs, const uint64_t *lwe_rhs, uint32_t log_p,
+                        uint64_t *lwe_out, size_t count) {
+    return guarded([&] {
+        if (!ctx || (!lwe_lhs && count) || (!lwe_rhs && count) || (!lwe_out && count)) fail("null argument");
+        const size_t lwe = ctx->big_dim() + 1;
+        if (words_overlap(lwe_out, count * lwe, lwe_lhs, count * lwe) ||
+            words_overlap(lwe_out, count * lwe, lwe_rhs, count * lwe))
+            fail("lwe_mult: out overlaps an input");
+        if (ctx->multi())
+            return split_rows(ctx, count, [&](TfheMi355Context *s, size_t a, size_t n) {
+                return tfhe_mi355_lwe_mult(s, lwe_lhs + a * lwe, lwe_rhs + a * lwe, log_p, lwe_out + a * lwe, n);
+            });
+        std::lock_guard<std::mutex> g(ctx->mu);
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        require_glwe_mult_shape(ctx);
+        validate_log_p(log_p);
+        require_rlk(ctx);
+        if (!ctx->pksk_ready) fail("packing keyswitching key not uploaded");
+        host_pair_call(
+            ctx, lwe_lhs, lwe_rhs, lwe, lwe_out, lwe, count, [&](size_t n) { return lwe_mult_scratch(ctx, n); },
+            [&](const uint64_t *l, const uint64_t *r, uint64_t *o, size_t n, void *sc, size_t sb, hipStream_t s) {
+                launch_lwe_mult_dev(ctx, l, r, log_p, o, n, sc, sb, s);
+            });
+    });
+}
+
+int tfhe_mi355_lwe_mult_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || !bytes) fail("null argument");
+        std::lock_guard<std::mutex> g(ctx->mu);
+        require_glwe_mult_shape(ctx);
+        if (!ctx->rlk_ready) fail("relinearization key not uploaded: the scratch is defined from its upload on");
+        if (!ctx->pksk_ready) fail("packing keyswitching key not uploaded: its decomposition sizes the scratch");
+        *bytes = lwe_mult_scratch(ctx, count);
+    });
+}
+
+int tfhe_mi355_lwe_mult_async(TfheMi355Context *ctx, const uint64_t *d_lwe_lhs, const uint64_t *d_lwe_rhs,
+                              uint32_t log_p, uint64_t *d_lwe_out, size_t count, void *d_scratch,
+                              size_t scratch_bytes, void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!d_lwe_lhs && count) || (!d_lwe_rhs && count) || (!d_lwe_out && count)) fail("null argument");
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        launch_lwe_mult_dev(ctx, d_lwe_lhs, d_lwe_rhs, log_p, d_lwe_out, count, d_scratch, scratch_bytes,
+                            (hipStream_t)stream);
     });
 }
 

@@ -383,6 +383,35 @@ int tfhe_mi355_client_gen_pfpksk_list(uint64_t seed, const uint64_t *in_sk, uint
     });
 }
 
+// GLWE relinearisation key of the fork's glwe_mult [k(k+1)/2][level][(k+1)N], levels stored L..1
+// (custom_relinearization_key_generation.rs:72-161): block n = i(i+1)/2 + j (j <= i) holds GLWE
+// encryptions under glwe_sk of the polynomial (S_i * S_j) << (64 - base_log*lvl), S_i * S_j the exact
+// negacyclic product of two key polynomials.  Every block draws from its own stream.
+int tfhe_mi355_client_gen_relinearization_key(uint64_t seed, const uint64_t *glwe_sk, uint32_t k, uint32_t N,
+                                              uint32_t base_log, uint32_t level, double std, uint64_t *rlk) {
+    return guard([&] {
+        if (!glwe_sk || !rlk) throw std::invalid_argument("null argument");
+        if (level == 0 || base_log == 0 || base_log > 31 || (uint64_t)base_log * level > 63)
+            throw std::invalid_argument("invalid decomposition");
+        if (k == 0 || N == 0) throw std::invalid_argument("invalid GLWE shape");
+        const size_t glwe_len = (size_t)(k + 1) * N;
+        std::vector<uint64_t> prod(N);
+        size_t n = 0;
+        for (uint32_t i = 0; i < k; i++)
+            for (uint32_t j = 0; j <= i; j++, n++) {
+                std::fill(prod.begin(), prod.end(), 0);
+                negacyclic_binary_add(prod.data(), glwe_sk + (size_t)i * N, glwe_sk + (size_t)j * N, (int)N);
+                Rng r(seed, 0x9000000ULL + n);
+                for (uint32_t l = 0; l < level; l++) {
+                    const uint32_t lvl = level - l;
+                    uint64_t *g = rlk + (n * level + l) * glwe_len;
+                    for (uint32_t c = 0; c < N; c++) g[(size_t)k * N + c] = prod[c] << (64 - base_log * lvl);
+                    glwe_encrypt_assign(r, g, glwe_sk, (int)k, (int)N, std);
+                }
+            }
+    });
+}
+
 // Seeded keys (the reference's SeededLweBootstrapKey / SeededLweKeyswitchKey with a
 // CompressionSeed, seeded_lwe_bootstrap_key_generation.rs, seeded_lwe_keyswitch_key_generation.rs):
 // masks from the AES-CTR stream of (mask_seed_lo, mask_seed_hi), noise from the engine's own RNG;

@@ -287,6 +287,32 @@ struct GlwePolyMulLaunch {
 };
 hipError_t launch_glwe_poly_mul(const GlwePolyMulLaunch &a, hipStream_t s);
 
+// GLWE x GLWE product with relinearisation (glwe_mult.hip; the fork's glwe_mult,
+// custom_glwe_glwe_product.rs:13-321), per pair c:
+//   tensor kernel: both GLWEs shifted right by 32 - log_p/2, then with (A, B), (A', B') their masks and bodies
+//     out.mask_i = A_i B' + A'_i B,  out.body = B B',  tr[n(i,i)] = A_i A'_i,  tr[n(i,j)] = A_i A'_j + A_j A'_i
+//     (j < i, n(i,j) = i(i+1)/2 + j), negacyclic products over Z/2^64;
+//   relinearisation kernel: out_q += sum_n sum_l digit_l(tr[n]) * rlk[n][l][q], digit 0 = level L (the key's
+//     first GLWE per block), SignedDecomposer(base_log, level).
+// extract: out holds the degree-0 sample of the result, [count][kN+1] (of the body only coefficient 0
+// is computed).
+struct GlweMultLaunch {
+    const uint64_t *lhs, *rhs;  // [count][(k+1)N]
+    uint64_t *out;              // [count][(k+1)N], or [count][kN+1] when extract
+    uint64_t *tr;               // scratch [count][k(k+1)/2][N] (glwe_mult_scratch_bytes)
+    const uint64_t *rlk;        // [k(k+1)/2][level][(k+1)N], the reference's layout
+    int k, N;
+    int log_p;                  // even, 0..64
+    int base_log, level;        // 1 <= base_log <= 31, base_log * level <= 63
+    int extract;
+    size_t count;
+    KernelTimer *timer = nullptr;
+};
+// N a power of two in [256, 2048], 1 <= k <= 5, (k+1) N <= 4096
+bool glwe_mult_supported(int N, int k);
+size_t glwe_mult_scratch_bytes(int N, int k, size_t count);
+hipError_t launch_glwe_mult(const GlweMultLaunch &a, hipStream_t s);
+
 // Batched GGSW x GLWE nodes (ggsw_ops.hip): out = base + G (x) d per node, every node with its own
 // Fourier GGSW and the decomposition (base_log, level; base_log * level <= 32) of the call.
 //   GGSW_EP    d = in1 (glwe_in), base = out (accumulated)      add_external_product_assign

@@ -13,6 +13,7 @@
 // of input coefficients and broadcast to the wave.
 #include <cstdlib>
 
+#include "decompose64.h"
 #include "engine.h"
 
 namespace tfhe_mi355 {
@@ -23,14 +24,6 @@ constexpr int KS_TC = 64;     // ciphertexts per workgroup
 constexpr int KS_CPT = 16;    // ciphertexts per thread
 constexpr int KS_IC = 8;      // input coefficients per LDS chunk
 constexpr int KS_MAXL = 16;   // max decomposition levels
-
-__device__ __forceinline__ uint64_t closest_repr(uint64_t x, int base_log, int level) {
-    int shift = 64 - base_log * level - 1;
-    uint64_t res = x >> shift;
-    res += 1;
-    res &= ~(uint64_t)1;
-    return res << shift;
-}
 }  // namespace
 
 __global__ void __launch_bounds__(256) keyswitch_kernel(KeyswitchLaunch a) {

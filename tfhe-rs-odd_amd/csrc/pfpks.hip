@@ -19,6 +19,7 @@
 //   sum d K = sum_b 2^(8b) (A0 K_b) + sum_b 2^(8b+8) (A1 K_b)           (mod 2^64)
 // and plane b+1 of A0 shares its weight with plane b of A1: one int32 accumulator per weight,
 // 8 + 7 int8 MFMAs per 32-row step (A1 K_7 has weight 2^64 and vanishes).
+#include "decompose64.h"
 #include "engine.h"
 
 namespace tfhe_mi355 {
@@ -29,14 +30,6 @@ constexpr int PF_TC = 64;      // ciphertexts per workgroup
 constexpr int PF_CPT = 16;     // ciphertexts per thread
 constexpr int PF_ROWS = 128;   // (input word, level) digit rows staged per LDS chunk
 constexpr int PF_DPARTS = 8;   // digit workgroups per ciphertext (MFMA form)
-
-__device__ __forceinline__ uint64_t pf_closest_repr(uint64_t x, int base_log, int level) {
-    int shift = 64 - base_log * level - 1;
-    uint64_t res = x >> shift;
-    res += 1;
-    res &= ~(uint64_t)1;
-    return res << shift;
-}
 }  // namespace
 
 __global__ void __launch_bounds__(256) pfpks_kernel(PfpksLaunch a) {
@@ -64,7 +57,7 @@ __global__ void __launch_bounds__(256) pfpks_kernel(PfpksLaunch a) {
             const int c = c0 + ci, i = i0 + ii;
             uint64_t state = 0;
             if (c < a.count && i < in_rows)
-                state = pf_closest_repr(a.lwe_in[(size_t)c * in_rows + i], beta, L) >> (64 - beta * L);
+                state = closest_repr(a.lwe_in[(size_t)c * in_rows + i], beta, L) >> (64 - beta * L);
             for (int l = 0; l < L; l++) {
                 uint64_t res = state & mask;
                 state >>= beta;
@@ -128,7 +121,7 @@ __global__ void __launch_bounds__(256) pfpks_digits_kernel(PfpksLaunch a, int8_t
     const int per = (in_rows + PF_DPARTS - 1) / PF_DPARTS, i0 = part * per, i1 = min(in_rows, i0 + per);
     int s0 = 0, s1 = 0;
     for (int i = i0 + threadIdx.x; i < i1; i += 256) {
-        uint64_t state = pf_closest_repr(x[i], beta, L) >> (64 - beta * L);
+        uint64_t state = closest_repr(x[i], beta, L) >> (64 - beta * L);
         for (int l = 0; l < L; l++) {
             uint64_t res = state & mask;
             state >>= beta;

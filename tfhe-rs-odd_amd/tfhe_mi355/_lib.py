@@ -106,6 +106,13 @@ SIGNATURES = [
     ("tfhe_mi355_packing_keyswitch", ctypes.c_int, [vp, u64p, u64p, sz]),
     ("tfhe_mi355_packing_keyswitch_async", ctypes.c_int, [vp, vp, vp, sz, vp, sz, vp]),
     ("tfhe_mi355_packing_keyswitch_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_relinearization_key_upload", ctypes.c_int, [vp, u64p, sz, ctypes.c_uint32, ctypes.c_uint32]),
+    ("tfhe_mi355_glwe_mult", ctypes.c_int, [vp, u64p, u64p, ctypes.c_uint32, ctypes.c_int, u64p, sz]),
+    ("tfhe_mi355_glwe_mult_async", ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_int, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_glwe_mult_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_lwe_mult", ctypes.c_int, [vp, u64p, u64p, ctypes.c_uint32, u64p, sz]),
+    ("tfhe_mi355_lwe_mult_async", ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_lwe_mult_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
     ("tfhe_mi355_glwe_poly_mul", ctypes.c_int, [vp, u64p, sz, u64p, sz, sz, ctypes.c_int, u64p]),
     ("tfhe_mi355_glwe_poly_mul_async", ctypes.c_int, [vp, vp, sz, vp, sz, sz, ctypes.c_int, vp, vp]),
     ("tfhe_mi355_ggsw_external_product", ctypes.c_int,
@@ -148,6 +155,9 @@ SIGNATURES = [
     ("tfhe_mi355_client_gen_packing_keyswitch_key", ctypes.c_int,
      [ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_double, u64p, ctypes.c_uint32]),
+    ("tfhe_mi355_client_gen_relinearization_key", ctypes.c_int,
+     [ctypes.c_uint64, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double,
+      u64p]),
     ("tfhe_mi355_bootstrap_key_upload_seeded", ctypes.c_int, [vp, u64p, sz, ctypes.c_uint64, ctypes.c_uint64]),
     ("tfhe_mi355_keyswitch_key_upload_seeded", ctypes.c_int, [vp, u64p, sz, ctypes.c_uint64, ctypes.c_uint64]),
     ("tfhe_mi355_csprng_mask_words", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, u64p, sz]),

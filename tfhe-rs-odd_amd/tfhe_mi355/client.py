@@ -101,6 +101,17 @@ def gen_pfpksk_list(seed, in_sk, glwe_sk, glwe_dimension, polynomial_size, base_
     return out
 
 
+def gen_relinearization_key(seed, glwe_sk, glwe_dimension, polynomial_size, base_log, level, std_dev) -> np.ndarray:
+    """GLWE relinearisation key of lwe_mult [k(k+1)/2][level][(k+1)N], level L first: block i(i+1)/2 + j
+    (j <= i) encrypts (S_i * S_j) << (64 - base_log*lvl) (custom_relinearization_key_generation.rs:72-161)."""
+    glwe_sk = np.ascontiguousarray(glwe_sk, dtype=np.uint64)
+    k, N = glwe_dimension, polynomial_size
+    out = np.empty((k * (k + 1) // 2, level, (k + 1) * N), dtype=np.uint64)
+    _lib.call("tfhe_mi355_client_gen_relinearization_key", seed, _ptr(glwe_sk), k, N, base_log, level, std_dev,
+              _ptr(out))
+    return out
+
+
 def _seed_parts(seed: int):
     return seed & 0xFFFFFFFFFFFFFFFF, (seed >> 64) & 0xFFFFFFFFFFFFFFFF
 

@@ -357,6 +357,52 @@ class Engine:
         _lib.call("tfhe_mi355_glwe_poly_mul", self._h, _ptr(g), J, _ptr(v), v.shape[0], count, int(extract), _ptr(out))
         return out
 
+    # -- GLWE x GLWE product with relinearisation (the gadget layer's lwe_mult) ------------------
+    def upload_relinearization_key(self, rlk: np.ndarray, base_log: int, level: int) -> None:
+        """RelinearizationKey [k(k+1)/2][level][(k+1)N], level L first (the reference's memory as it is);
+        its decomposition belongs to the key."""
+        k = _u64(rlk)
+        _lib.call("tfhe_mi355_relinearization_key_upload", self._h, _ptr(k), k.size, base_log, level)
+
+    def glwe_mult(self, lhs, rhs, log_p: int, extract: bool = False) -> np.ndarray:
+        """glwe_mult (custom_glwe_glwe_product.rs:13-64), batched: both [count][(k+1)N] GLWEs shifted right
+        by 32 - log_p/2, tensored and relinearised; with extract the degree-0 sample, [count][kN+1]."""
+        a = _u64(lhs).reshape(-1, self.glwe_len)
+        b = _u64(rhs).reshape(-1, self.glwe_len)
+        if a.shape != b.shape:
+            raise ValueError("glwe_mult: lhs and rhs differ in shape")
+        out = np.empty((a.shape[0], self.big_dim + 1 if extract else self.glwe_len), dtype=np.uint64)
+        _lib.call("tfhe_mi355_glwe_mult", self._h, _ptr(a), _ptr(b), log_p, int(extract), _ptr(out), a.shape[0])
+        return out
+
+    def lwe_mult(self, lhs, rhs, log_p: int) -> np.ndarray:
+        """The ciphertext half of lwe_mult (gadget/engine/mod.rs:680-751), batched: both [count][kN+1] LWEs
+        packed by one packing-keyswitch launch, multiplied, sample-extracted."""
+        a = _u64(lhs).reshape(-1, self.big_dim + 1)
+        b = _u64(rhs).reshape(-1, self.big_dim + 1)
+        if a.shape != b.shape:
+            raise ValueError("lwe_mult: lhs and rhs differ in shape")
+        out = np.empty_like(a)
+        _lib.call("tfhe_mi355_lwe_mult", self._h, _ptr(a), _ptr(b), log_p, _ptr(out), a.shape[0])
+        return out
+
+    def glwe_mult_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_glwe_mult_scratch", count)
+
+    def lwe_mult_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_lwe_mult_scratch", count)
+
+    def glwe_mult_async(self, d_lhs, d_rhs, log_p: int, extract: bool, d_out, count: int, stream=None,
+                        d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.glwe_mult_scratch_bytes(count), stream)
+        _lib.call("tfhe_mi355_glwe_mult_async", self._h, _dev_ptr(d_lhs), _dev_ptr(d_rhs), log_p, int(extract),
+                  _dev_ptr(d_out), count, sp, sb, _stream_ptr(stream))
+
+    def lwe_mult_async(self, d_lhs, d_rhs, log_p: int, d_out, count: int, stream=None, d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.lwe_mult_scratch_bytes(count), stream)
+        _lib.call("tfhe_mi355_lwe_mult_async", self._h, _dev_ptr(d_lhs), _dev_ptr(d_rhs), log_p, _dev_ptr(d_out),
+                  count, sp, sb, _stream_ptr(stream))
+
     # -- GGSW operations: per-item GGSW ciphertexts, decomposition chosen per call -----------
     def ggsw_words(self, level: int) -> int:
         """u64 words of one standard-domain GGSW: [level][k+1][(k+1)N]."""

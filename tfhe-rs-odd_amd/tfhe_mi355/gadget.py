@@ -13,6 +13,8 @@ maps one encoding to another, executed as batched keyswitch + PBS launches of th
                                          gadget/engine/mod.rs:263-322
   Bootstrapper::keyswitch_bootstrap      gadget/engine/bootstrapping.rs:828-884
   bootstrap_without_sample_extract       fft64/crypto/bootstrap.rs:383-412 (Engine.blind_rotate)
+  GadgetEngine::lwe_mult, woppbs_lut     gadget/engine/mod.rs:677-803 (Engine.lwe_mult: packing
+                                         keyswitch + glwe_mult, custom_glwe_glwe_product.rs:13-321)
 
 The fork's msgpack noise dumps ("cjp" patterns) are not reproduced.  Batched forms take many
 independent gadget evaluations and issue one GPU launch for all of them.
@@ -332,8 +334,8 @@ class ServerKey:
     """gadget ServerKey (engine/bootstrapping.rs:261-345; server_key/mod.rs) on the engine.
 
     Holds the bootstrapping key (Fourier, in HBM), the LWE keyswitching key and -- created on
-    first use by mvb/tree bootstrapping -- the LWE -> GLWE packing keyswitching key.  The GLWE
-    relinearisation key of the "even transistor" lwe_mult is not built (out of scope).
+    first use by mvb/tree bootstrapping and by lwe_mult -- the LWE -> GLWE packing keyswitching key
+    and the GLWE relinearisation key of the "even transistor" (lwe_mult, woppbs_lut).
     Every method has a *_batch form that evaluates many independent inputs in one launch per
     step; the single forms mirror the reference's signatures."""
 
@@ -352,6 +354,7 @@ class ServerKey:
         self.engine.upload_keyswitch_key(ksk)
         self.pbs_order = "KeyswitchBootstrap" if p.encryption_key_choice == "Big" else "BootstrapKeyswitch"
         self._pksk_ready = False
+        self._rlk_ready = False
 
     # -- key material ----------------------------------------------------------------------
     def _require_packing_key(self):
@@ -365,6 +368,17 @@ class ServerKey:
                                                 p.glwe_modular_std_dev)
         self.engine.upload_packing_keyswitch_key(pksk, p.ks_base_log, p.ks_level)
         self._pksk_ready = True
+
+    def _require_relinearization_key(self):
+        """allocate_and_generate_new_relinearization_key (bootstrapping.rs:367-374): products of the
+        GLWE key's polynomials under the GLWE key, with the KS decomposition and the GLWE noise."""
+        if self._rlk_ready:
+            return
+        p = self.parameters
+        rlk = client.gen_relinearization_key(self._ck_seed * 7 + 6, self._glwe_key, p.glwe_dimension,
+                                             p.polynomial_size, p.ks_base_log, p.ks_level, p.glwe_modular_std_dev)
+        self.engine.upload_relinearization_key(rlk, p.ks_base_log, p.ks_level)
+        self._rlk_ready = True
 
     @property
     def _lwe_size(self) -> int:
@@ -521,6 +535,51 @@ class ServerKey:
 
     def full_tree_bootstrapping(self, inputs, encodings_out, t: int, f) -> list:
         return self.full_tree_bootstrapping_batch([inputs], encodings_out, t, f)[0]
+
+    # -- the even transistor (engine/mod.rs:677-803) -------------------------------------------
+    def lwe_mult_batch(self, lhs, rhs, output_encoding: Encoding) -> list:
+        """lwe_mult (engine/mod.rs:680-751) for many independent pairs: both LWEs packed to GLWEs by the
+        packing keyswitch, multiplied with relinearisation (glwe_mult, log_p = ilog2 of the common
+        modulus, which must be even) and sample-extracted, in ONE engine call.  The inputs' encodings
+        only have to share their modulus; the result takes output_encoding."""
+        assert len(lhs) == len(rhs)
+        if not all(isinstance(c, Ciphertext) for c in list(lhs) + list(rhs)):
+            raise ValueError("Calling LweMult with trivial ciphertexts")
+        if self.pbs_order != "KeyswitchBootstrap":
+            raise NotImplementedError("lwe_mult: BootstrapKeyswitch order (the inputs must be under the big key)")
+        p = lhs[0].encoding.get_modulus()
+        assert all(c.encoding.get_modulus() == p for c in list(lhs) + list(rhs)), "lwe_mult: unequal moduli"
+        log_p = p.bit_length() - 1
+        assert log_p % 2 == 0, f"lwe_mult: log2(p) = {log_p} is odd"
+        self._require_packing_key()
+        self._require_relinearization_key()
+        out = self.engine.lwe_mult(np.stack([c.ct for c in lhs]), np.stack([c.ct for c in rhs]), log_p)
+        return [Ciphertext(out[i].copy(), output_encoding) for i in range(len(lhs))]
+
+    def lwe_mult(self, lhs: Ciphertext, rhs: Ciphertext, output_encoding: Encoding) -> Ciphertext:
+        return self.lwe_mult_batch([lhs], [rhs], output_encoding)[0]
+
+    def woppbs_lut_batch(self, inputs, encoding_out: Encoding, f) -> list:
+        """woppbs_lut (engine/mod.rs:755-802) over inputs sharing one (WoP-PBS, even p) encoding: two
+        bootstrapping launches over the batch -- ct_f with the input encoding pushed through f, ct_ones
+        onto Encoding.new_all_one_wopbs, whose negacyclic sign cancels ct_f's -- then one lwe_mult.
+        As in the reference, the wopbs accumulator spreads its p windows over half the torus, so an
+        input encoded at x * 2^64/p reads window 2x mod p: on Encoding.new_trivial_wopbs(p) inputs the
+        chain returns f(2x mod p), not f(x)."""
+        if not all(isinstance(c, Ciphertext) for c in inputs):
+            raise ValueError("woppbs_lut on a trivial ciphertext")
+        enc_in = inputs[0].encoding
+        assert all(c.encoding == enc_in for c in inputs)
+        enc_inter = enc_in.apply_lut_to_encoding(f)
+        enc_ones = Encoding.new_all_one_wopbs(enc_in.get_origin_modulus())
+        x = np.stack([c.ct for c in inputs])
+        ct_f = self._bootstrap_pattern(x, fill_lookup_table(self.parameters, enc_inter, encoding_out))
+        ct_ones = self._bootstrap_pattern(x, fill_lookup_table(self.parameters, enc_in, enc_ones))
+        return self.lwe_mult_batch([Ciphertext(ct_f[i], encoding_out) for i in range(len(inputs))],
+                                   [Ciphertext(ct_ones[i], enc_ones) for i in range(len(inputs))], encoding_out)
+
+    def woppbs_lut(self, ct: Ciphertext, encoding_out: Encoding, f) -> Ciphertext:
+        return self.woppbs_lut_batch([ct], encoding_out, f)[0]
 
     def trivial_encrypt(self, message: int) -> int:
         """Ciphertext::Trivial (engine/mod.rs:97-99) is a bare integer in the reference."""
