@@ -429,8 +429,16 @@ int tfhe_mi355_ggsw_list_convert_async(TfheMi355Context *ctx, const uint64_t *d_
  * cmux_tree_memory_optimized :468-592, blind_rotate_assign :866-892).  Fails when npoly is not a
  * power of two, when log2(npoly) > nbits (the reference then skips the tree and reads one
  * polynomial only), when nbits - log2(npoly) > log2(N), or when nbits = 0.
+ * Launches: one per tree level, over count * (npoly >> (level + 1)) CMUX nodes, then one for the whole
+ * blind rotation: every item's nbits - log2(npoly) rotation steps and its sample extraction run back
+ * to back inside it (timer families ggsw_cmux_tree, ggsw_rotate_chain).  Without rotation bits the last
+ * tree level extracts.  TFHE_MI355_VP_STEPWISE=1 launches the rotation steps one by one instead
+ * (ggsw_rotate; same results, for A/B runs).  TFHE_MI355_GGSW_GRID=<n>, read at every launch, caps the
+ * workgroups of a GGSW launch (a test hook: the persistent node loop then wraps at small counts).
  * The _async form takes the Fourier GGSW list and tfhe_mi355_vertical_packing_scratch bytes of device
- * scratch (the tree's ping-pong accumulators); a NULL or short scratch fails. */
+ * scratch (the tree's two ping-pong accumulator lists, count * max(npoly/2, 1) and count * max(npoly/4, 1)
+ * GLWEs, each rounded up to 256 bytes; the first also holds the rotation's accumulators); a NULL or short
+ * scratch fails. */
 int tfhe_mi355_vertical_packing(TfheMi355Context *ctx, const uint64_t *ggsw_list, uint32_t base_log, uint32_t level,
                                 uint32_t nbits, const uint64_t *luts, size_t lut_count, size_t npoly,
                                 const uint32_t *lut_indexes, size_t count, uint64_t *lwe_out);
@@ -489,8 +497,12 @@ int tfhe_mi355_circuit_bootstrap_scratch(TfheMi355Context *ctx, uint32_t cbs_lev
 /* circuit_bootstrap_boolean_vertical_packing (wop_pbs/mod.rs:647-746): lwe_in [count][nbits][n+1], one
  * bit per ciphertext at q/2, most significant first (what tfhe_mi355_extract_bits writes);
  * luts [lut_count][nout][npoly][N] with lut_indexes [count] (NULL: LUT 0); lwe_out [count][nout][k*N+1].
- * Circuit bootstrap, Fourier conversion, then one vertical packing per output o on polynomials
- * [o*npoly, (o+1)*npoly) of the item's LUT, under the same GGSWs. */
+ * Circuit bootstrap, Fourier conversion, then ONE vertical packing over (item, output): output o reads
+ * polynomials [o*npoly, (o+1)*npoly) of the item's LUT in place, under the item's GGSWs, so a tree level
+ * is one launch over count * nout * (npoly >> (level + 1)) nodes, the rotation one chain launch over
+ * count * nout nodes, and the last launch writes lwe_out[item][o] directly (no per-output pass, no LUT
+ * gather or output scatter).  Scratch: [standard GGSWs | Fourier GGSWs | max(circuit bootstrap scratch,
+ * the vertical packing's ping-pong lists scaled by nout)]; the query returns exactly that. */
 int tfhe_mi355_circuit_bootstrap_vertical_packing(TfheMi355Context *ctx, const uint64_t *lwe_in, uint32_t nbits,
                                                   uint32_t cbs_base_log, uint32_t cbs_level, const uint64_t *luts,
                                                   size_t lut_count, size_t nout, size_t npoly,
@@ -512,6 +524,30 @@ int tfhe_mi355_keyswitch_async(TfheMi355Context *ctx, const uint64_t *d_lwe_in, 
                                size_t count, void *d_scratch, size_t scratch_bytes, void *stream);
 /* Device scratch (bytes) of the async keyswitch: the int8-MFMA path's digit matrix. */
 int tfhe_mi355_keyswitch_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+
+/* A keyswitching key as an object of its own, with dimensions no parameter set of the context needs to
+ * describe (the keyswitches between a PBS and a WoP-PBS parameter set: big key -> big key of another
+ * set, big key -> small key of another set).  ksk is [in_dim][level][out_dim+1], levels L..1: the memory
+ * and level order tfhe_mi355_keyswitch_key_upload takes; len must be in_dim * level * (out_dim + 1).
+ * Fails on a zero dimension, base_log = 0, level = 0 or base_log * level >= 64.  The key lives on every
+ * device of a multi-device context and must be destroyed before the context.
+ * tfhe_mi355_keyswitch_with_key: lwe_in count x (in_dim+1) -> lwe_out count x (out_dim+1), the same
+ * kernels as tfhe_mi355_keyswitch (int8 MFMA GEMMs where the decomposition allows it, the scalar kernel
+ * otherwise; timer family keyswitch); the host form splits the rows over the devices.  The _async form
+ * takes tfhe_mi355_keyswitch_with_key_scratch bytes (the MFMA form's digit matrix; 0 for the scalar
+ * kernel); a NULL or short scratch fails. */
+typedef struct TfheMi355KeyswitchKey TfheMi355KeyswitchKey;
+int tfhe_mi355_lwe_keyswitch_key_create(TfheMi355Context *ctx, const uint64_t *ksk, size_t len, size_t in_dim,
+                                        size_t out_dim, uint32_t base_log, uint32_t level,
+                                        TfheMi355KeyswitchKey **key);
+int tfhe_mi355_lwe_keyswitch_key_destroy(TfheMi355KeyswitchKey *key);
+int tfhe_mi355_keyswitch_with_key(TfheMi355Context *ctx, const TfheMi355KeyswitchKey *key, const uint64_t *lwe_in,
+                                  uint64_t *lwe_out, size_t count);
+int tfhe_mi355_keyswitch_with_key_async(TfheMi355Context *ctx, const TfheMi355KeyswitchKey *key,
+                                        const uint64_t *d_lwe_in, uint64_t *d_lwe_out, size_t count, void *d_scratch,
+                                        size_t scratch_bytes, void *stream);
+int tfhe_mi355_keyswitch_with_key_scratch(TfheMi355Context *ctx, const TfheMi355KeyswitchKey *key, size_t count,
+                                          size_t *bytes);
 
 /* shortint KS -> PBS (PBSOrder::KeyswitchBootstrap): lwe_in/out count x (k*N+1).
  * Replaces ServerKey::keyswitch_programmable_bootstrap_assign (shortint/server_key/mod.rs:783-857). */

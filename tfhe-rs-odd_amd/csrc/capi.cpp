@@ -314,6 +314,25 @@ struct TfheMi355Context {
     size_t rlk_len(uint32_t level) const { return k() * (k() + 1) / 2 * level * glwe_len(); }
 };
 
+// A keyswitching key of its own dimensions and decomposition (tfhe_mi355_lwe_keyswitch_key_create): one
+// copy per distinct device of its context, read-only after creation.
+struct TfheMi355KeyswitchKey {
+    TfheMi355Context *ctx = nullptr;
+    size_t in_dim = 0, out_dim = 0;
+    uint32_t base_log = 0, level = 0;
+    bool mfma = false;  // int8 byte planes built: the MFMA form runs
+    struct Part {
+        int device = 0;
+        DeviceBuffer ksk, planes;
+    };
+    std::vector<std::unique_ptr<Part>> parts;
+    const Part *on(int device) const {
+        for (auto &p : parts)
+            if (p->device == device) return p.get();
+        return nullptr;
+    }
+};
+
 namespace {
 
 // ---- key transactions ------------------------------------------------------------------------
@@ -672,6 +691,34 @@ void launch_ks_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, s
     check(launch_keyswitch(a, s), "launch keyswitch");
 }
 
+// keyswitch under a key object, on shard (or single-device context) c
+size_t ks_key_scratch_bytes(const TfheMi355KeyswitchKey *key, size_t count) {
+    return key->mfma && count ? ks_mfma_scratch_bytes((int)key->in_dim, (int)key->level, (int)count) : 0;
+}
+void launch_ks_key_dev(TfheMi355Context *c, const TfheMi355KeyswitchKey *key, const uint64_t *d_in, uint64_t *d_out,
+                       size_t count, void *scratch, size_t scratch_bytes, hipStream_t s) {
+    const TfheMi355KeyswitchKey::Part *part = key->on(c->device);
+    if (!part) fail("keyswitching key has no copy on device %d", c->device);
+    if (count == 0) return;
+    if (count > 0x7fffffffu) fail("count too large");
+    KeyswitchLaunch a;
+    a.lwe_in = d_in;
+    a.lwe_out = d_out;
+    a.ksk = reinterpret_cast<const uint64_t *>(part->ksk.ptr);
+    a.in_dim = (int)key->in_dim;
+    a.out_dim = (int)key->out_dim;
+    a.base_log = (int)key->base_log;
+    a.level = (int)key->level;
+    a.count = (int)count;
+    TimedLaunch tl(c->timer_or_null(), "keyswitch", s);
+    if (key->mfma) {
+        require_scratch(scratch ? scratch_bytes : 0, ks_key_scratch_bytes(key, count));
+        check(launch_keyswitch_mfma(a, (const int8_t *)part->planes.ptr, scratch, s), "launch mfma keyswitch");
+        return;
+    }
+    check(key->base_log > 7 ? launch_keyswitch_wide(a, s) : launch_keyswitch(a, s), "launch keyswitch");
+}
+
 // LWE -> GLWE packing keyswitch (lwe_packing_keyswitch.rs:102-186): the LWE keyswitch GEMM with
 // (k+1)N-word GLWE rows and the input body landing on the GLWE body's constant term
 KeyswitchLaunch packing_ks_args(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, size_t count) {
@@ -945,31 +992,42 @@ VpShape vp_shape(const TfheMi355Context *c, uint32_t nbits, size_t npoly) {
     return {nt, nbits - nt};
 }
 
-// two ping-pong GLWE buffers: the tree's first level leaves npoly/2 nodes per item, the next npoly/4
-size_t vp_scratch_bytes(const TfheMi355Context *c, size_t npoly, size_t count) {
+// two ping-pong GLWE buffers per (item, output): the tree's first level leaves npoly/2 nodes, the next
+// npoly/4; without a tree the first holds the rotation steps' accumulator
+size_t vp_scratch_bytes(const TfheMi355Context *c, size_t npoly, size_t nout, size_t count) {
     const size_t a = std::max<size_t>(npoly / 2, 1), b = std::max<size_t>(npoly / 4, 1);
-    return align256(count * a * c->glwe_len() * 8) + align256(count * b * c->glwe_len() * 8);
+    return align256(count * nout * a * c->glwe_len() * 8) + align256(count * nout * b * c->glwe_len() * 8);
 }
 
+// TFHE_MI355_VP_STEPWISE=1: one launch per rotation step instead of the chain launch (A/B arm); read at
+// every call, so that one process can run both arms
+bool vp_stepwise() { return env_flag("TFHE_MI355_VP_STEPWISE"); }
+
+// luts [lut_count][nout][npoly][N], d_lwe_out [count][nout][kN+1]: every launch covers the nout outputs
+// of every item (GgswCmuxLaunch::nout), so a tree level is one launch over count nout (npoly >> (j+1))
+// nodes and the rotation steps are one chain launch over count nout nodes
 void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, uint32_t base_log, uint32_t level,
-                                 uint32_t nbits, const uint64_t *d_luts, size_t lut_count, size_t npoly,
+                                 uint32_t nbits, const uint64_t *d_luts, size_t lut_count, size_t nout, size_t npoly,
                                  const uint32_t *d_lut_idx, size_t count, uint64_t *d_lwe_out, void *scratch,
                                  size_t scratch_bytes, hipStream_t s) {
     require_ggsw_shape(c, base_log, level);
     const VpShape sh = vp_shape(c, nbits, npoly);
     if (lut_count == 0 || lut_count > 0xffffffffu) fail("lut_count out of range");
+    if (nout == 0 || nout > 0xffffu) fail("vertical packing: nout %zu out of range", nout);
     if (count == 0) return;
-    if (count * std::max<size_t>(npoly / 2, 1) > 0x7fffffffu) fail("count too large");
-    require_scratch(scratch ? scratch_bytes : 0, vp_scratch_bytes(c, npoly, count));
+    if (count > 0x7fffffffu / (nout * std::max<size_t>(npoly / 2, 1))) fail("count too large");
+    require_scratch(scratch ? scratch_bytes : 0, vp_scratch_bytes(c, npoly, nout, count));
     const size_t glwe = c->glwe_len();
-    uint64_t *buf[2] = {reinterpret_cast<uint64_t *>(scratch),
-                        reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(scratch) +
-                                                     align256(count * std::max<size_t>(npoly / 2, 1) * glwe * 8))};
+    uint64_t *buf[2] = {
+        reinterpret_cast<uint64_t *>(scratch),
+        reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(scratch) +
+                                     align256(count * nout * std::max<size_t>(npoly / 2, 1) * glwe * 8))};
     GgswCmuxLaunch a = ggsw_launch_args(c, d_fggsw, count, nullptr, base_log, level);
     a.ggsw_per_item = (int)nbits;
     a.lut_indexes = d_lut_idx;
     a.lut_count = (uint32_t)lut_count;
     a.npoly = (int)npoly;
+    a.nout = (int)nout;
     const uint64_t *cur = nullptr;  // the accumulators so far (null: still the LUT itself)
     // CMUX tree, level by level: layer j pairs the nodes (2i, 2i+1) of the layer before under GGSW
     // nt-1-j (the list is most significant bit first; cmux_tree_memory_optimized walks it reversed)
@@ -979,7 +1037,7 @@ void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, ui
         a.leaf = cur == nullptr;
         a.ggsw_sel = (int)(sh.nt - 1 - j);
         a.nodes_per_item = npoly >> (j + 1);
-        a.nodes = count * a.nodes_per_item;
+        a.nodes = count * nout * a.nodes_per_item;
         a.in0 = cur ? cur : d_luts;
         a.in1 = cur ? cur + glwe : nullptr;
         a.in_stride = 2 * glwe;
@@ -989,7 +1047,26 @@ void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, ui
         check(launch_ggsw_cmux((int)c->N(), (int)c->k(), a, s), "launch CMUX tree level");
         cur = a.out;
     }
-    // blind rotation by the remaining GGSWs, last first, monomial degrees 1, 2, 4, ... (in place)
+    // blind rotation by the remaining GGSWs, last first, monomial degrees 1, 2, 4, ... (in place): one
+    // chain launch runs every step and the sample extraction
+    if (sh.nr && !vp_stepwise()) {
+        a.mode = GGSW_ROT;
+        a.leaf = cur == nullptr;
+        a.ggsw_sel = (int)(nbits - 1);
+        a.rot = 1;
+        a.chain = (int)sh.nr;
+        a.nodes_per_item = 1;
+        a.nodes = count * nout;
+        a.in0 = cur ? cur : d_luts;
+        a.in1 = nullptr;
+        a.in_stride = glwe;
+        a.acc = cur ? const_cast<uint64_t *>(cur) : buf[0];
+        a.extract = 1;
+        a.out = d_lwe_out;
+        TimedLaunch tl(c->timer_or_null(), "ggsw_rotate_chain", s);
+        check(launch_ggsw_cmux((int)c->N(), (int)c->k(), a, s), "launch rotation chain");
+        return;
+    }
     for (uint32_t i = 0; i < sh.nr; i++) {
         const bool last = i + 1 == sh.nr;
         a.mode = GGSW_ROT;
@@ -997,7 +1074,7 @@ void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, ui
         a.ggsw_sel = (int)(nbits - 1 - i);
         a.rot = 1 << i;
         a.nodes_per_item = 1;
-        a.nodes = count;
+        a.nodes = count * nout;
         a.in0 = cur ? cur : d_luts;
         a.in1 = nullptr;
         a.in_stride = glwe;
@@ -1170,21 +1247,19 @@ void launch_cbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t delta_lo
 
 // circuit_bootstrap_boolean_vertical_packing (wop_pbs/mod.rs:647-746): lwe_in [count][nbits] bits at
 // q/2, luts [lut_count][nout][npoly][N]; output o of an item is the vertical packing of polynomials
-// [o npoly, (o+1) npoly) of its LUT, under the same GGSWs.  One pass of the vertical packing per
-// output, on the pass's LUT slice gathered into [lut_count][npoly][N].
-// scratch = [standard GGSWs | Fourier GGSWs | LUT slice | pass output | circuit bootstrap or vertical packing scratch]
+// [o npoly, (o+1) npoly) of its LUT, under the same GGSWs: one vertical packing over (item, output).
+// scratch = [standard GGSWs | Fourier GGSWs | circuit bootstrap or vertical packing scratch]
 struct CbvpLayout {
-    size_t std_b, four_b, lut_b, out_b, rest_b;
-    size_t total() const { return std_b + four_b + lut_b + out_b + rest_b; }
+    size_t std_b, four_b, rest_b;
+    size_t total() const { return std_b + four_b + rest_b; }
 };
 CbvpLayout cbvp_layout(const TfheMi355Context *c, uint32_t nbits, uint32_t level, size_t nout, size_t npoly,
                        size_t lut_count, size_t count) {
     CbvpLayout l;
     l.std_b = align256(count * nbits * ggsw_std_words(c, level) * 8);
     l.four_b = align256(count * nbits * ggsw_fourier_bytes(c, level));
-    l.lut_b = nout > 1 ? align256(lut_count * npoly * c->N() * 8) : 0;
-    l.out_b = nout > 1 ? align256(count * (c->big_dim() + 1) * 8) : 0;
-    l.rest_b = std::max(cbs_scratch_bytes(c, level, count * nbits), std::max<size_t>(vp_scratch_bytes(c, npoly, count), 256));
+    l.rest_b = std::max(cbs_scratch_bytes(c, level, count * nbits),
+                        std::max<size_t>(vp_scratch_bytes(c, npoly, nout, count), 256));
     return l;
 }
 void launch_cbvp_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t nbits, uint32_t base_log, uint32_t level,
@@ -1202,27 +1277,11 @@ void launch_cbvp_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t nbits, 
     char *p = reinterpret_cast<char *>(scratch);
     uint64_t *ggsw_std = reinterpret_cast<uint64_t *>(p);
     double2 *ggsw_f = reinterpret_cast<double2 *>(p + l.std_b);
-    uint64_t *lut_slice = reinterpret_cast<uint64_t *>(p + l.std_b + l.four_b);
-    uint64_t *pass_out = reinterpret_cast<uint64_t *>(p + l.std_b + l.four_b + l.lut_b);
-    void *rest = p + l.std_b + l.four_b + l.lut_b + l.out_b;
+    void *rest = p + l.std_b + l.four_b;
     launch_cbs_dev(c, d_in, 63, base_log, level, ggsw_std, count * nbits, rest, l.rest_b, s);
     ggsw_list_to_fourier_dev(c, ggsw_std, ggsw_f, count * nbits, level, s);
-    if (nout == 1) {
-        launch_vertical_packing_dev(c, ggsw_f, base_log, level, nbits, d_luts, lut_count, npoly, d_lut_idx, count, d_out,
-                                    rest, l.rest_b, s);
-        return;
-    }
-    const size_t slice = npoly * c->N() * 8, ow = (c->big_dim() + 1) * 8;
-    for (size_t o = 0; o < nout; o++) {
-        check(hipMemcpy2DAsync(lut_slice, slice, reinterpret_cast<const char *>(d_luts) + o * slice, nout * slice, slice,
-                               lut_count, hipMemcpyDeviceToDevice, s),
-              "gather LUT slice");
-        launch_vertical_packing_dev(c, ggsw_f, base_log, level, nbits, lut_slice, lut_count, npoly, d_lut_idx, count,
-                                    pass_out, rest, l.rest_b, s);
-        check(hipMemcpy2DAsync(reinterpret_cast<char *>(d_out) + o * ow, nout * ow, pass_out, ow, ow, count,
-                               hipMemcpyDeviceToDevice, s),
-              "scatter pass output");
-    }
+    launch_vertical_packing_dev(c, ggsw_f, base_log, level, nbits, d_luts, lut_count, nout, npoly, d_lut_idx, count,
+                                d_out, rest, l.rest_b, s);
 }
 
 void validate_lut_indexes(const uint32_t *idx, size_t count, size_t lut_count) {
@@ -3110,7 +3169,7 @@ int tfhe_mi355_vertical_packing_scratch(TfheMi355Context *ctx, size_t npoly, siz
         if (!ctx || !bytes) fail("null argument");
         if (npoly == 0 || npoly > 0x40000000u || !is_pow2((uint32_t)npoly))
             fail("vertical packing: the LUT has %zu polynomials, not a power of two", npoly);
-        *bytes = vp_scratch_bytes(ctx, npoly, count);
+        *bytes = vp_scratch_bytes(ctx, npoly, 1, count);
     });
 }
 
@@ -3123,7 +3182,7 @@ int tfhe_mi355_vertical_packing_async(TfheMi355Context *ctx, const void *d_fouri
         if (!ctx || (!d_fourier_ggsw && count) || !d_luts || (!d_lwe_out && count)) fail("null argument");
         check(hipSetDevice(ctx->device), "hipSetDevice");
         launch_vertical_packing_dev(ctx, (const double2 *)d_fourier_ggsw, base_log, level, nbits, d_luts, lut_count,
-                                    npoly, d_lut_indexes, count, d_lwe_out, d_scratch, scratch_bytes,
+                                    1, npoly, d_lut_indexes, count, d_lwe_out, d_scratch, scratch_bytes,
                                     (hipStream_t)stream);
     });
 }
@@ -3158,7 +3217,7 @@ int tfhe_mi355_vertical_packing(TfheMi355Context *ctx, const uint64_t *ggsw_list
         d_f.reserve(chunk * item_f);
         d_luts.reserve(lut_b);
         d_out.reserve(chunk * out_w * 8);
-        d_scr.reserve(std::max<size_t>(vp_scratch_bytes(ctx, npoly, chunk), 256));
+        d_scr.reserve(std::max<size_t>(vp_scratch_bytes(ctx, npoly, 1, chunk), 256));
         if (lut_indexes) d_idx.reserve(chunk * 4);
         hipStream_t s = ctx->stream;
         check(hipMemcpyAsync(d_luts.ptr, luts, lut_b, hipMemcpyHostToDevice, s), "H2D luts");
@@ -3170,7 +3229,7 @@ int tfhe_mi355_vertical_packing(TfheMi355Context *ctx, const uint64_t *ggsw_list
                 check(hipMemcpyAsync(d_idx.ptr, lut_indexes + a, n * 4, hipMemcpyHostToDevice, s), "H2D lut indexes");
             ggsw_list_to_fourier_dev(ctx, (const uint64_t *)d_std.ptr, (double2 *)d_f.ptr, n * nbits, level, s);
             launch_vertical_packing_dev(ctx, (const double2 *)d_f.ptr, base_log, level, nbits,
-                                        (const uint64_t *)d_luts.ptr, lut_count, npoly, (const uint32_t *)d_idx.ptr, n,
+                                        (const uint64_t *)d_luts.ptr, lut_count, 1, npoly, (const uint32_t *)d_idx.ptr, n,
                                         (uint64_t *)d_out.ptr, d_scr.ptr, d_scr.bytes, s);
             check(hipMemcpyAsync(lwe_out + a * out_w, d_out.ptr, n * out_w * 8, hipMemcpyDeviceToHost, s), "D2H out");
             check(hipStreamSynchronize(s), "vertical packing sync");
@@ -3488,6 +3547,105 @@ int tfhe_mi355_keyswitch_async(TfheMi355Context *ctx, const uint64_t *d_in, uint
         if (!ctx || (!d_in && count) || (!d_out && count)) fail("null argument");
         check(hipSetDevice(ctx->device), "hipSetDevice");
         launch_ks_dev(ctx, d_in, d_out, count, d_scratch, scratch_bytes, (hipStream_t)stream);
+    });
+}
+
+int tfhe_mi355_lwe_keyswitch_key_create(TfheMi355Context *ctx, const uint64_t *ksk, size_t len, size_t in_dim,
+                                        size_t out_dim, uint32_t base_log, uint32_t level,
+                                        TfheMi355KeyswitchKey **key) {
+    return guarded([&] {
+        if (!ctx || !ksk || !key) fail("null argument");
+        *key = nullptr;
+        if (in_dim == 0 || out_dim == 0) fail("keyswitching key: zero dimension (in_dim %zu, out_dim %zu)", in_dim, out_dim);
+        if (in_dim > 0x3fffffffu || out_dim > 0x3fffffffu) fail("keyswitching key: dimension too large");
+        if (base_log == 0 || level == 0 || (uint64_t)base_log * level >= 64)
+            fail("keyswitching key: decomposition base_log %u x level %u out of range (base_log * level < 64)", base_log,
+                 level);
+        if (len != in_dim * level * (out_dim + 1))
+            fail("keyswitching key has %zu words, expected %zu", len, in_dim * level * (out_dim + 1));
+        static const bool no_mfma = env_flag("TFHE_MI355_KS_NO_MFMA");
+        const bool mfma = !no_mfma && ks_mfma_supported((int)in_dim, (int)level, (int)base_log);
+        if (!mfma && !keyswitch_scalar_supported((int)base_log, (int)level))
+            fail("keyswitching key: no kernel for base_log %u x level %u (base_log <= 15, level <= 16)", base_log, level);
+        std::unique_ptr<TfheMi355KeyswitchKey> k(new TfheMi355KeyswitchKey);
+        k->ctx = ctx;
+        k->in_dim = in_dim;
+        k->out_dim = out_dim;
+        k->base_log = base_log;
+        k->level = level;
+        k->mfma = mfma;
+        std::vector<TfheMi355Context *> where = ctx->multi() ? ctx->shards : std::vector<TfheMi355Context *>{ctx};
+        for (TfheMi355Context *c : where) {
+            if (k->on(c->device)) continue;
+            check(hipSetDevice(c->device), "hipSetDevice");
+            std::unique_ptr<TfheMi355KeyswitchKey::Part> part(new TfheMi355KeyswitchKey::Part);
+            part->device = c->device;
+            part->ksk.reserve(len * sizeof(uint64_t));
+            check(hipMemcpy(part->ksk.ptr, ksk, len * sizeof(uint64_t), hipMemcpyHostToDevice), "upload ksk");
+            if (mfma) {
+                std::lock_guard<std::mutex> g(c->mu);  // the repack runs on the context's stream
+                part->planes.reserve(8 * ks_mfma_rows((int)in_dim, (int)level) * ks_mfma_cols((int)out_dim));
+                check(launch_ksk_repack((const uint64_t *)part->ksk.ptr, (int8_t *)part->planes.ptr, (int)in_dim,
+                                        (int)level, (int)out_dim, c->stream),
+                      "ksk repack");
+                check(hipStreamSynchronize(c->stream), "ksk repack sync");
+            }
+            k->parts.push_back(std::move(part));
+        }
+        *key = k.release();
+    });
+}
+
+int tfhe_mi355_lwe_keyswitch_key_destroy(TfheMi355KeyswitchKey *key) {
+    return guarded([&] {
+        if (!key) return;
+        for (auto &p : key->parts) {
+            (void)hipSetDevice(p->device);
+            p->ksk.release();
+            p->planes.release();
+        }
+        delete key;
+    });
+}
+
+int tfhe_mi355_keyswitch_with_key(TfheMi355Context *ctx, const TfheMi355KeyswitchKey *key, const uint64_t *lwe_in,
+                                  uint64_t *lwe_out, size_t count) {
+    return guarded([&] {
+        if (!ctx || !key || (!lwe_in && count) || (!lwe_out && count)) fail("null argument");
+        if (key->ctx != ctx && key->ctx != ctx->owner) fail("keyswitching key belongs to another context");
+        const size_t wi = key->in_dim + 1, wo = key->out_dim + 1;
+        if (ctx->multi())
+            return split_rows(ctx, count, [&](TfheMi355Context *s, size_t a, size_t n) {
+                return tfhe_mi355_keyswitch_with_key(s, key, lwe_in + a * wi, lwe_out + a * wo, n);
+            });
+        std::lock_guard<std::mutex> g(ctx->mu);
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        host_wop_call(
+            ctx, lwe_in, wi, lwe_out, wo, nullptr, count, kWopChunkRows,
+            [&](size_t n) { return ks_key_scratch_bytes(key, n); },
+            [&](const uint64_t *i, uint64_t *o, const uint32_t *, size_t n, void *sc, size_t sb, hipStream_t s) {
+                launch_ks_key_dev(ctx, key, i, o, n, sc, sb, s);
+            });
+    });
+}
+
+int tfhe_mi355_keyswitch_with_key_scratch(TfheMi355Context *ctx, const TfheMi355KeyswitchKey *key, size_t count,
+                                          size_t *bytes) {
+    return guarded([&] {
+        if (!ctx || !key || !bytes) fail("null argument");
+        *bytes = ks_key_scratch_bytes(key, count);
+    });
+}
+
+int tfhe_mi355_keyswitch_with_key_async(TfheMi355Context *ctx, const TfheMi355KeyswitchKey *key,
+                                        const uint64_t *d_lwe_in, uint64_t *d_lwe_out, size_t count, void *d_scratch,
+                                        size_t scratch_bytes, void *stream) {
+    return guarded([&] {
+        if (!ctx || !key || (!d_lwe_in && count) || (!d_lwe_out && count)) fail("null argument");
+        if (key->ctx != ctx && key->ctx != ctx->owner) fail("keyswitching key belongs to another context");
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        launch_ks_key_dev(ctx, key, d_lwe_in, d_lwe_out, count, d_scratch, scratch_bytes, (hipStream_t)stream);
     });
 }
 

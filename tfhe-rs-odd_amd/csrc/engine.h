@@ -220,6 +220,9 @@ struct KeyswitchLaunch {
     __host__ __device__ int body() const { return body_col < 0 ? out_dim : body_col; }
 };
 hipError_t launch_keyswitch(const KeyswitchLaunch &a, hipStream_t s);
+// the scalar kernel with 16-bit digits (8 <= base_log <= 15); decompositions either scalar launch takes
+hipError_t launch_keyswitch_wide(const KeyswitchLaunch &a, hipStream_t s);
+bool keyswitch_scalar_supported(int base_log, int level);
 // int8-MFMA keyswitch: KSK repacked once into 8 byte planes (ks_mfma_cols x ks_mfma_rows each)
 bool ks_mfma_supported(int in_dim, int level, int base_log);
 size_t ks_mfma_rows(int in_dim, int level);
@@ -322,8 +325,14 @@ hipError_t launch_glwe_mult(const GlweMultLaunch &a, hipStream_t s);
 // with block(item) = ggsw_indexes[item] (clamped to ggsw_blocks - 1) or item.  Its operands sit at
 // in0 / in1 + nd * in_stride words, its output at out + nd * (k+1)N (or nd * (kN+1) when extract:
 // degree-0 sample extraction of the result).  leaf: the operands are trivial GLWEs (zero mask) whose
-// bodies are polynomials of the item's LUT, in0 = luts [lut_count][npoly][N]: polynomials 2s, 2s+1
-// for node s of the item (CMUX), polynomial s (ROT).
+// bodies are polynomials of the item's LUT, in0 = luts [lut_count][nout][npoly][N]: polynomials 2s, 2s+1
+// of output o for node s of the item (CMUX), polynomial s (ROT).
+// nout > 1 adds an output dimension between the item and its nodes: node nd is node nd % nodes_per_item
+// of output (nd / nodes_per_item) % nout of item nd / (nodes_per_item nout); the GGSW depends on the
+// item alone, the leaves of output o are read in place from the LUT's slice o.
+// chain > 0 (GGSW_ROT, nodes_per_item 1): the node runs `chain` rotation steps in the one launch, step i
+// under GGSW ggsw_sel - i with degree rot << i, then writes out / extracts as a single step does after
+// the last; acc [nodes][(k+1)N] holds the running accumulators (it may be in0 when not leaf).
 enum GgswMode { GGSW_EP = 0, GGSW_CMUX = 1, GGSW_ROT = 2 };
 struct GgswCmuxLaunch {
     const double2 *fggsw;          // [ggsw_blocks][ggsw_per_item][L][k+1][k+1] polys, engine Fourier layout
@@ -336,6 +345,9 @@ struct GgswCmuxLaunch {
     uint32_t lut_count;
     int npoly;                     // leaf: polynomials per LUT
     int mode, leaf, rot, extract;
+    int nout = 1;                  // outputs per item (LUT slices under one set of GGSWs)
+    int chain = 0;                 // rotation steps run inside the launch (0: one plain node)
+    uint64_t *acc = nullptr;       // chain: the nodes' accumulator slots
     size_t nodes, nodes_per_item;
     size_t in_stride;
     int base_log, level;

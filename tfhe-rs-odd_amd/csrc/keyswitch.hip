@@ -26,8 +26,10 @@ constexpr int KS_IC = 8;      // input coefficients per LDS chunk
 constexpr int KS_MAXL = 16;   // max decomposition levels
 }  // namespace
 
+// Digit: int8_t for base_log <= 7 (|d| <= 64), int16_t for the wider digits of launch_keyswitch_wide
+template <class Digit>
 __global__ void __launch_bounds__(256) keyswitch_kernel(KeyswitchLaunch a) {
-    __shared__ int8_t dig[KS_IC][KS_MAXL][KS_TC];
+    __shared__ Digit dig[KS_IC][KS_MAXL][KS_TC];
     const int tid = threadIdx.x;
     const int tj = tid & 63, tg = tid >> 6;
     const int j = blockIdx.x * KS_TJ + tj;
@@ -56,7 +58,7 @@ __global__ void __launch_bounds__(256) keyswitch_kernel(KeyswitchLaunch a) {
                 uint64_t carry = ((res - 1) | state) & res;
                 carry >>= beta - 1;
                 state += carry;
-                dig[ii][l][ci] = (int8_t)(int64_t)(res - (carry << beta));
+                dig[ii][l][ci] = (Digit)(int64_t)(res - (carry << beta));
             }
         }
         __syncthreads();
@@ -262,8 +264,22 @@ hipError_t launch_keyswitch(const KeyswitchLaunch &a, hipStream_t s) {
     if (a.count == 0) return hipSuccess;
     if (a.level > KS_MAXL || a.base_log * a.level >= 64 || a.base_log > 7) return hipErrorInvalidValue;
     dim3 grid((a.out_dim + 1 + KS_TJ - 1) / KS_TJ, (a.count + KS_TC - 1) / KS_TC);
-    hipLaunchKernelGGL(keyswitch_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(keyswitch_kernel<int8_t>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
+}
+
+// the same kernel with 16-bit digits: 8 <= base_log <= 15 (|d| <= 2^14), for keys whose decomposition
+// is not one of a parameter set's (tfhe_mi355_lwe_keyswitch_key_create)
+hipError_t launch_keyswitch_wide(const KeyswitchLaunch &a, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
+    if (a.level > KS_MAXL || a.base_log * a.level >= 64 || a.base_log < 8 || a.base_log > 15) return hipErrorInvalidValue;
+    dim3 grid((a.out_dim + 1 + KS_TJ - 1) / KS_TJ, (a.count + KS_TC - 1) / KS_TC);
+    hipLaunchKernelGGL(keyswitch_kernel<int16_t>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+bool keyswitch_scalar_supported(int base_log, int level) {
+    return base_log >= 1 && base_log <= 15 && level >= 1 && level <= KS_MAXL && base_log * level < 64;
 }
 
 }  // namespace tfhe_mi355

@@ -77,6 +77,12 @@ SIGNATURES = [
     ("tfhe_mi355_keyswitch", ctypes.c_int, [vp, u64p, u64p, sz]),
     ("tfhe_mi355_keyswitch_async", ctypes.c_int, [vp, vp, vp, sz, vp, sz, vp]),
     ("tfhe_mi355_keyswitch_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_lwe_keyswitch_key_create", ctypes.c_int,
+     [vp, u64p, sz, sz, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]),
+    ("tfhe_mi355_lwe_keyswitch_key_destroy", ctypes.c_int, [vp]),
+    ("tfhe_mi355_keyswitch_with_key", ctypes.c_int, [vp, vp, u64p, u64p, sz]),
+    ("tfhe_mi355_keyswitch_with_key_async", ctypes.c_int, [vp, vp, vp, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_keyswitch_with_key_scratch", ctypes.c_int, [vp, vp, sz, ctypes.POINTER(sz)]),
     ("tfhe_mi355_keyswitch_programmable_bootstrap", ctypes.c_int, [vp, u64p, u64p, u64p, sz, u32p, sz]),
     ("tfhe_mi355_keyswitch_programmable_bootstrap_async", ctypes.c_int,
      [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp]),

@@ -261,6 +261,34 @@ class Engine:
         _lib.call("tfhe_mi355_keyswitch", self._h, _ptr(x), _ptr(out), x.shape[0])
         return out
 
+    # -- keyswitching keys as objects (the keyswitches between two parameter sets) ---------------
+    def keyswitch_key(self, ksk, in_dim: int, out_dim: int, base_log: int, level: int) -> "KeyswitchKey":
+        """A keyswitching key [in_dim][level][out_dim+1] (levels L..1, as upload_keyswitch_key takes it) of
+        its own dimensions and decomposition, on every device of the engine."""
+        k = _u64(ksk).ravel()
+        h = vp()
+        _lib.call("tfhe_mi355_lwe_keyswitch_key_create", self._h, _ptr(k), k.size, in_dim, out_dim, base_log, level,
+                  ctypes.byref(h))
+        return KeyswitchKey(self, h, in_dim, out_dim, base_log, level)
+
+    def keyswitch_with_key(self, key: "KeyswitchKey", lwe_in) -> np.ndarray:
+        """keyswitch_lwe_ciphertext under `key`, batched: [count][in_dim+1] -> [count][out_dim+1]."""
+        x = _u64(lwe_in).reshape(-1, key.in_dim + 1)
+        out = np.empty((x.shape[0], key.out_dim + 1), dtype=np.uint64)
+        _lib.call("tfhe_mi355_keyswitch_with_key", self._h, key._handle(self), _ptr(x), _ptr(out), x.shape[0])
+        return out
+
+    def keyswitch_with_key_scratch_bytes(self, key: "KeyswitchKey", count: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call("tfhe_mi355_keyswitch_with_key_scratch", self._h, key._handle(self), count, ctypes.byref(b))
+        return b.value
+
+    def keyswitch_with_key_async(self, key: "KeyswitchKey", d_in, d_out, count: int, stream=None,
+                                 d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.keyswitch_with_key_scratch_bytes(key, count), stream)
+        _lib.call("tfhe_mi355_keyswitch_with_key_async", self._h, key._handle(self), _dev_ptr(d_in), _dev_ptr(d_out),
+                  count, sp, sb, _stream_ptr(stream))
+
     def keyswitch_programmable_bootstrap(self, lwe_in, luts, lut_indexes=None, out=None) -> np.ndarray:
         x = _u64(lwe_in).reshape(-1, self.big_dim + 1)
         L = self._luts(luts)
@@ -710,6 +738,33 @@ def fill_accumulator(params: ClassicPBSParameters, f) -> np.ndarray:
     cp = c_params(params)
     _lib.call("tfhe_mi355_fill_accumulator", ctypes.byref(cp), _ptr(fv), _ptr(acc))
     return acc
+
+
+class KeyswitchKey:
+    """Handle of a keyswitching key object (Engine.keyswitch_key); it keeps its engine alive and is freed
+    with the last reference (or close())."""
+
+    def __init__(self, engine: Engine, handle, in_dim: int, out_dim: int, base_log: int, level: int):
+        self.engine, self._h = engine, handle
+        self.in_dim, self.out_dim, self.base_log, self.level = in_dim, out_dim, base_log, level
+
+    def _handle(self, engine: Engine):
+        if engine is not self.engine:
+            raise ValueError("keyswitching key belongs to another engine")
+        if not self._h or not self._h.value:
+            raise ValueError("keyswitching key already closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            _lib.call("tfhe_mi355_lwe_keyswitch_key_destroy", self._h)
+            self._h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Request:

@@ -16,6 +16,10 @@ operand pairs at once:
                                                             radix_parallel/mod.rs:88-155
   ServerKey.blockshift                                      radix/scalar_mul.rs:345-355
   shortint unchecked_apply_lookup_table_bivariate_assign    shortint/server_key/bivariate_pbs.rs:69-182
+  WopbsKey (wopbs, wopbs_without_padding, bivariate_wopbs_with_degree, generate_lut_radix,
+  generate_lut_radix_without_padding, generate_lut_bivariate_radix, keyswitch_to_wopbs_params,
+  keyswitch_to_pbs_params), encode_radix, encode_mix_radix, decode_radix,
+  split_value_according_to_bit_basis                        integer/wopbs/mod.rs:94-195, 216-629, 784-844
 
 Execution model.  The reference's DAG depends only on block degrees and noise levels, never on
 the encrypted values, so K operand pairs with the same input shape follow the same DAG.  A
@@ -38,7 +42,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .shortint import KEYSWITCH_BOOTSTRAP, NOISE_NOMINAL, NOISE_ZERO, LookupTable, ServerKey as ShortintServerKey
+from .shortint import (KEYSWITCH_BOOTSTRAP, NOISE_NOMINAL, NOISE_ZERO, LookupTable, ServerKey as ShortintServerKey,
+                       WopbsKey as ShortintWopbsKey)
 
 OUTPUT_CARRY_NONE, OUTPUT_CARRY_GENERATED, OUTPUT_CARRY_PROPAGATED = 0, 1, 2  # add.rs:13-21
 
@@ -572,6 +577,243 @@ class ServerKey:
         return self.unchecked_mul(lhs, rhs)
 
 
+# ---- integer WoP-PBS (integer/wopbs/mod.rs) ----------------------------------------------------------
+_U64 = (1 << 64) - 1
+
+
+def encode_radix(val: int, basis: int, nb_block: int) -> list:
+    """The nb_block digits of val in a power-of-two basis, least significant first."""
+    mask, power, out = basis - 1, 1, []
+    for _ in range(nb_block):
+        out.append((val & (mask * power)) // power)
+        power *= basis
+    return out
+
+
+def encode_mix_radix(val: int, basis: list, modulus: int) -> list:
+    """val read as fields of basis[i] bits, least significant first: each field gives its digit modulo
+    `modulus`, and what it holds above the digit's bits is carried into the fields that follow."""
+    log_mod = int(np.log2(modulus))
+    out = []
+    for bits in basis:
+        digit = val % modulus
+        out.append(digit)
+        val -= digit
+        carry = (val % (1 << bits)) >> log_mod
+        val = (val >> bits) + carry
+    return out
+
+
+def decode_radix(val: list, basis: int) -> int:
+    result, shift = 0, 1
+    for v in val:
+        result = (result + v * shift) & _U64
+        shift = (shift * basis) & _U64
+    return result
+
+
+def split_value_according_to_bit_basis(value: int, basis: list) -> list:
+    out = []
+    for bits in basis:
+        out.append(value & ((1 << bits) - 1))
+        value >>= bits
+    return out
+
+
+def _ceil_log2(x: int) -> int:
+    return (x - 1).bit_length()
+
+
+class WopbsKey:
+    """integer WopbsKey (integer/wopbs/mod.rs) on RadixBatch: K integers share one degree vector, so their
+    bit extractions and the composed call are batched over K.
+
+    Execution.  Blocks are taken most significant first; blocks with the same number of bits go through
+    ONE extract_bits call; the bits are concatenated to [K][total_bits][n+1] and ONE composed call follows
+    (circuit bootstrap + vertical packing) with as many outputs as the LUT has, under one set of GGSWs.
+    Host arrays are the path: a device-resident batch is brought to the host and the result returned in
+    the residency it came in.  The engines are only reached through extract_bits,
+    circuit_bootstrap_vertical_packing, keyswitch_with_key, keyswitch and the PBS calls."""
+
+    def __init__(self, wopbs_key: ShortintWopbsKey):
+        self.wopbs_key = wopbs_key
+
+    @staticmethod
+    def _shortint(key):
+        """the shortint key inside an integer ClientKey / ServerKey (or the shortint key itself)."""
+        return getattr(key, "key", None) or getattr(key, "shortint", None) or key
+
+    @classmethod
+    def new_wopbs_key(cls, cks, sks, parameters, device: int = 0, engine=None) -> "WopbsKey":
+        return cls(ShortintWopbsKey.new_wopbs_key(cls._shortint(cks), cls._shortint(sks), parameters, device, engine))
+
+    @classmethod
+    def new_from_shortint(cls, wopbs_key: ShortintWopbsKey) -> "WopbsKey":
+        return cls(wopbs_key)
+
+    @classmethod
+    def new_wopbs_key_only_for_wopbs(cls, cks, sks) -> "WopbsKey":
+        return cls(ShortintWopbsKey.new_wopbs_key_only_for_wopbs(cls._shortint(cks), cls._shortint(sks)))
+
+    @property
+    def param(self):
+        return self.wopbs_key.param
+
+    # -- residency ---------------------------------------------------------------------------
+    @staticmethod
+    def _host(rb: RadixBatch):
+        """(host u64 array, function putting a host array back where rb's data lives)."""
+        if isinstance(rb.data, np.ndarray):
+            return np.ascontiguousarray(rb.data, dtype=np.uint64), lambda a: a
+        import torch
+
+        dev = rb.data.device
+        return (rb.data.cpu().numpy().view(np.uint64),
+                lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev))
+
+    # -- lookup tables -------------------------------------------------------------------------
+    def _lut_size(self, total_bit: int) -> int:
+        return max(self.param.polynomial_size, 1 << total_bit)
+
+    def _delta(self) -> int:
+        return (1 << 63) // (self.param.message_modulus * self.param.carry_modulus)
+
+    def generate_lut_radix(self, ct: RadixBatch, f) -> np.ndarray:
+        """integer/wopbs/mod.rs:523-565: [blocks][max(N, 2^total_bit)], block j indexed through
+        ceil(log2(degree_j + 1)) bits, one bit of padding."""
+        basis = self.param.message_modulus
+        nb = ct.num_blocks
+        deg_bits = [_ceil_log2(d + 1) for d in ct.degree]
+        total_bit, modulus, delta = sum(deg_bits), basis ** nb, self._delta()
+        lut = np.zeros((nb, self._lut_size(total_bit)), dtype=np.uint64)
+        for idx in range(1 << total_bit):
+            value = decode_radix(encode_mix_radix(idx, deg_bits, basis), basis)
+            f_val = int(f(value % modulus)) % modulus
+            for o, digit in enumerate(encode_radix(f_val, basis, nb)):
+                lut[o, idx] = np.uint64((digit * delta) & _U64)
+        return lut
+
+    def generate_lut_radix_without_padding(self, ct: RadixBatch, f) -> np.ndarray:
+        """integer/wopbs/mod.rs:593-629: every block indexed through all log2(message carry) bits; the carry
+        bits of a block fold onto the message bits of the next."""
+        p = self.param
+        log_msg, log_carry = int(np.log2(p.message_modulus)), int(np.log2(p.carry_modulus))
+        log_basis = log_msg + log_carry
+        nb = ct.num_blocks
+        size = self._lut_size(nb * log_basis)
+        lut = np.zeros((nb, size), dtype=np.uint64)
+        for index in range(size):
+            value, rest = 0, index
+            for i in range(nb):
+                field = rest % (1 << (log_basis * (i + 1)))
+                rest -= field
+                value += field >> (log_carry * i)
+            f_val = int(f(value))
+            for o in range(nb):
+                lut[o, index] = np.uint64((((f_val >> (log_carry * o)) % (1 << log_msg)) << (64 - log_basis)) & _U64)
+        return lut
+
+    def generate_lut_bivariate_radix(self, ct1: RadixBatch, ct2: RadixBatch, f) -> np.ndarray:
+        """integer/wopbs/mod.rs:784-844: the index's low bits are ct1's, the bits above ct2's."""
+        basis = self.param.message_modulus
+        nb = ct1.num_blocks
+        deg_bits = [[_ceil_log2(d + 1) for d in ct.degree] for ct in (ct1, ct2)]
+        nbits = [sum(b) for b in deg_bits]
+        modulus, delta = basis ** ct2.num_blocks, self._delta()
+        lut = np.zeros((nb, self._lut_size(sum(nbits))), dtype=np.uint64)
+        for idx in range(1 << sum(nbits)):
+            split = (idx % (1 << nbits[0]), idx >> nbits[0])
+            x, y = (decode_radix(encode_mix_radix(split[i], deg_bits[i], basis), basis) for i in range(2))
+            f_val = int(f(x % modulus, y % modulus)) % modulus
+            for o, digit in enumerate(encode_radix(f_val, basis, nb)):
+                lut[o, idx] = np.uint64((digit * delta) & _U64)
+        return lut
+
+    # -- the WoP-PBS ---------------------------------------------------------------------------
+    def _wopbs(self, ct_in: RadixBatch, lut, nbits: list, delta_log: int) -> RadixBatch:
+        p = self.param
+        eng = self.wopbs_key.engine
+        data, back = self._host(ct_in)
+        K, nb = data.shape[0], data.shape[1]
+        order = [j for j in range(nb - 1, -1, -1) if nbits[j]]      # most significant block first
+        if not order:
+            raise ValueError("wopbs: no bit to extract (every block has degree 0)")
+        groups = {}
+        for j in order:
+            groups.setdefault(nbits[j], []).append(j)
+        bits_of = {}
+        for n, blocks in groups.items():                           # one extract_bits call per bit count
+            b = eng.extract_bits(np.concatenate([data[:, j, :] for j in blocks]), delta_log, n)
+            for q, j in enumerate(blocks):
+                bits_of[j] = b[q * K:(q + 1) * K]
+        bits = np.concatenate([bits_of[j] for j in order], axis=1)  # [K][total_bits][n+1]
+        lut = np.ascontiguousarray(lut, dtype=np.uint64)
+        if lut.ndim != 2 or lut.shape[1] != self._lut_size(bits.shape[1]):
+            raise ValueError(f"wopbs: the LUT must be [outputs][{self._lut_size(bits.shape[1])}] for "
+                             f"{bits.shape[1]} extracted bits")
+        out = self.wopbs_key.circuit_bootstrapping_vertical_packing(lut, bits)
+        keep = min(nb, lut.shape[0])                                # zip(blocks, outputs)
+        return RadixBatch(back(np.ascontiguousarray(out[:, :keep])), [p.message_modulus - 1] * keep,
+                          [NOISE_NOMINAL] * keep)
+
+    def wopbs(self, ct_in: RadixBatch, lut) -> RadixBatch:
+        """integer/wopbs/mod.rs:277-341: one bit of padding, ceil(log2(degree + 1)) bits per block."""
+        p = self.param
+        delta_log = ((1 << 63) // (p.message_modulus * p.carry_modulus)).bit_length() - 1
+        return self._wopbs(ct_in, lut, [_ceil_log2(d + 1) for d in ct_in.degree], delta_log)
+
+    def wopbs_without_padding(self, ct_in: RadixBatch, lut) -> RadixBatch:
+        """integer/wopbs/mod.rs:365-428: no padding bit, log2(message carry) bits per block."""
+        p = self.param
+        block_modulus = p.message_modulus * p.carry_modulus
+        delta_log = ((1 << 63) // (block_modulus // 2)).bit_length() - 1
+        return self._wopbs(ct_in, lut, [int(np.log2(block_modulus))] * ct_in.num_blocks, delta_log)
+
+    def bivariate_wopbs_with_degree(self, ct1: RadixBatch, ct2: RadixBatch, lut) -> RadixBatch:
+        """integer/wopbs/mod.rs:487-493: wopbs of ct1's blocks followed by ct2's; the LUT's outputs pair with
+        the first blocks, ct1's."""
+        d1, _ = self._host(ct1)
+        d2, _ = self._host(ct2)
+        _, back = self._host(ct1)
+        both = RadixBatch(np.concatenate([d1, d2], axis=1), list(ct1.degree) + list(ct2.degree),
+                          list(ct1.noise) + list(ct2.noise))
+        res = self.wopbs(both, lut)
+        return RadixBatch(back(res.data), res.degree, res.noise)
+
+    # -- between the PBS and the WoP parameter sets --------------------------------------------
+    def keyswitch_to_wopbs_params(self, sks, ct_in: RadixBatch) -> RadixBatch:
+        """shortint keyswitch_to_wopbs_params (wopbs/mod.rs:724-754) on every block: ONE identity KS+PBS
+        launch under the PBS set over the non-trivial blocks, ONE keyswitch PBS big key -> WoP big key over
+        all of them.  Degrees are kept."""
+        wk = self.wopbs_key
+        if wk.ksk_pbs_to_wopbs is None:
+            raise ValueError("keyswitch_to_wopbs_params: a key only for wopbs has no PBS -> WoP keyswitching key")
+        s = self._shortint(sks)
+        data, back = self._host(ct_in)
+        K, nb, w = data.shape
+        clean = data.copy()
+        live = [j for j in range(nb) if ct_in.noise[j] != NOISE_ZERO]
+        if live:
+            acc = s.generate_lookup_table(lambda x: x)
+            rows = np.ascontiguousarray(data[:, live, :]).reshape(-1, w)
+            clean[:, live, :] = s.engine_ks_pbs(rows, acc.acc).reshape(K, len(live), w)
+        out = wk.engine.keyswitch_with_key(wk.ksk_pbs_to_wopbs, clean.reshape(K * nb, w))
+        return RadixBatch(back(out.reshape(K, nb, -1)), list(ct_in.degree), [NOISE_NOMINAL] * nb)
+
+    def keyswitch_to_pbs_params(self, ct_in: RadixBatch) -> RadixBatch:
+        """shortint keyswitch_to_pbs_params (wopbs/mod.rs:660-722) on every block: ONE keyswitch WoP big key
+        -> PBS small key, ONE identity PBS under the PBS set."""
+        wk = self.wopbs_key
+        ps = wk.pbs_server_key
+        data, back = self._host(ct_in)
+        K, nb, w = data.shape
+        rows = data.reshape(K * nb, w)
+        small = ps.engine.keyswitch(rows) if wk.ksk_wopbs_to_pbs is None else \
+            ps.engine.keyswitch_with_key(wk.ksk_wopbs_to_pbs, rows)
+        out = ps.engine.programmable_bootstrap(small, ps.generate_lookup_table(lambda x: x).acc)
+        return RadixBatch(back(out.reshape(K, nb, -1)), list(ct_in.degree), [NOISE_NOMINAL] * nb)
+
+
 class ClientKey:
     """integer RadixClientKey over a shortint ClientKey (integer/client_key/radix.rs)."""
 
@@ -601,5 +843,29 @@ class ClientKey:
         for j in range(rb.num_blocks):
             raw = client.lwe_decrypt(self.key.large_lwe_secret_key, np.ascontiguousarray(rb.data[:, j, :]))
             d = client.decode(raw, p.delta) % np.uint64(p.message_modulus)
+            out += d << np.uint64(bits * j)
+        return out
+
+    def encrypt_without_padding(self, values) -> RadixBatch:
+        """The radix digits under the encoding without a padding bit (shortint encrypt_without_padding)."""
+        p = self.key.parameters
+        v = np.asarray(values, dtype=np.uint64)
+        bits = int(np.log2(p.message_modulus))
+        digits = [(v >> np.uint64(bits * j)) % np.uint64(p.message_modulus) for j in range(self.num_blocks)]
+        blocks = [self.key.encrypt_without_padding_many(d) for d in digits]
+        data = np.stack([np.stack([c.ct for c in blk]) for blk in blocks], axis=1)
+        return RadixBatch(data, [p.message_modulus - 1] * self.num_blocks, [NOISE_NOMINAL] * self.num_blocks)
+
+    def decrypt_without_padding(self, rb: RadixBatch) -> np.ndarray:
+        p = self.key.parameters
+        from . import client
+
+        if not isinstance(rb.data, np.ndarray):
+            rb = RadixBatch(rb.data.cpu().numpy().view(np.uint64), rb.degree, rb.noise)
+        bits = int(np.log2(p.message_modulus))
+        out = np.zeros(rb.count, dtype=np.uint64)
+        for j in range(rb.num_blocks):
+            raw = client.lwe_decrypt(self.key.large_lwe_secret_key, np.ascontiguousarray(rb.data[:, j, :]))
+            d = client.decode(raw, 2 * p.delta) % np.uint64(p.message_modulus)
             out += d << np.uint64(bits * j)
         return out

@@ -13,6 +13,9 @@
                                                             engine/client_side.rs:273-317, client_key/mod.rs:424-483
   WopbsKey.new_wopbs_key_only_for_wopbs / generate_lut[_without_padding] / wopbs /
   programmable_bootstrapping_without_padding                wopbs/mod.rs:235-495, 825-857
+  WopbsKey.new_wopbs_key                                    engine/wopbs/mod.rs:50-183
+  WopbsKey.keyswitch_to_wopbs_params / keyswitch_to_pbs_params / programmable_bootstrapping /
+  extract_bits / circuit_bootstrapping_vertical_packing     wopbs/mod.rs:398-408, 547-754
 
 Batched forms (`apply_lookup_table_batch`) hand a whole layer of independent ciphertexts to the
 GPU in one launch -- the shape the integer layer produces (radix_parallel/mul.rs:347-407).
@@ -287,15 +290,60 @@ class WopbsKey:
     """shortint WopbsKey (wopbs/mod.rs) on the engine of its server key: the circuit bootstrap's private
     functional packing keyswitching keys next to the bootstrapping and keyswitching keys."""
 
-    def __init__(self, wopbs_server_key: ServerKey, param: WopbsParameters, pfpksk: np.ndarray | None = None):
+    def __init__(self, wopbs_server_key: ServerKey, param: WopbsParameters, pfpksk: np.ndarray | None = None, *,
+                 pbs_server_key: ServerKey | None = None, ksk_pbs_to_wopbs=None, ksk_wopbs_to_pbs=None):
+        """pbs_server_key: the PBS set's server key (None: the WoP set is the PBS set, a key "only for
+        wopbs").  ksk_pbs_to_wopbs: keyswitching key object PBS big key -> WoP big key on the WoP engine;
+        ksk_wopbs_to_pbs: WoP big key -> PBS small key on the PBS server key's engine (the reference's
+        pbs_server_key.key_switching_key)."""
         if not isinstance(param, WopbsParameters):
             raise ValueError("WopbsKey needs WopbsParameters")
         if param.pbs_level > 4:
             raise ValueError(f"pbs_level {param.pbs_level}: no classic PBS kernel for WoP-PBS sets of 5 or 6 levels")
         self.wopbs_server_key = wopbs_server_key
+        self.pbs_server_key = pbs_server_key if pbs_server_key is not None else wopbs_server_key
+        self.ksk_pbs_to_wopbs = ksk_pbs_to_wopbs
+        self.ksk_wopbs_to_pbs = ksk_wopbs_to_pbs
         self.param = param
+        self._wopbs_client_key = None
         if pfpksk is not None:
             wopbs_server_key.engine.upload_pfpksk_list(pfpksk, param.pfks_base_log, param.pfks_level)
+
+    @classmethod
+    def new_wopbs_key(cls, cks: ClientKey, sks: ServerKey, parameters: WopbsParameters, device: int = 0,
+                      engine=None) -> "WopbsKey":
+        """engine/wopbs/mod.rs:50-183: secret keys of the WoP set's own, its bootstrapping, keyswitching and
+        pfpks keys on a second engine (`engine`, or a new Engine on `device`), and the two keyswitching
+        keys between the sets.  Every seed derives from cks.seed."""
+        if not isinstance(parameters, WopbsParameters):
+            raise ValueError("new_wopbs_key: parameters are no WopbsParameters")
+        if parameters.grouping_factor or cks.parameters.grouping_factor:
+            raise ValueError("new_wopbs_key: multi-bit keys are not supported (the reference refuses them)")
+        p, pp = parameters, cks.parameters
+        wcks = ClientKey(p, cks.seed * 7 + 6)
+        s = wcks.seed
+        bsk = client.gen_bootstrap_key(s * 7 + 3, wcks.small_lwe_secret_key, wcks.glwe_secret_key, p.glwe_dimension,
+                                       p.polynomial_size, p.pbs_base_log, p.pbs_level, p.glwe_modular_std_dev)
+        ksk = client.gen_keyswitch_key(s * 7 + 4, wcks.large_lwe_secret_key, wcks.small_lwe_secret_key, p.ks_base_log,
+                                       p.ks_level, p.lwe_modular_std_dev)
+        pfpksk = client.gen_pfpksk_list(s * 7 + 5, wcks.large_lwe_secret_key, wcks.glwe_secret_key, p.glwe_dimension,
+                                        p.polynomial_size, p.pfks_base_log, p.pfks_level, p.pfks_modular_std_dev)
+        # PBS big key -> WoP big key: the PBS set's keyswitch decomposition, the WoP set's LWE noise
+        to_wop = client.gen_keyswitch_key(cks.seed * 7 + 8, cks.large_lwe_secret_key, wcks.large_lwe_secret_key,
+                                          pp.ks_base_log, pp.ks_level, p.lwe_modular_std_dev)
+        # WoP big key -> PBS small key: the PBS set's decomposition and noise
+        to_pbs = client.gen_keyswitch_key(cks.seed * 7 + 9, wcks.large_lwe_secret_key, cks.small_lwe_secret_key,
+                                          pp.ks_base_log, pp.ks_level, pp.lwe_modular_std_dev)
+        wop_engine = engine if engine is not None else Engine(p, device)
+        wsks = ServerKey(None, engine=wop_engine, bsk=bsk, ksk=ksk, parameters=p)
+        wsks.pbs_order = sks.pbs_order
+        key = cls(wsks, p, pfpksk, pbs_server_key=sks,
+                  ksk_pbs_to_wopbs=wop_engine.keyswitch_key(to_wop, pp.big_lwe_dimension, p.big_lwe_dimension,
+                                                            pp.ks_base_log, pp.ks_level),
+                  ksk_wopbs_to_pbs=sks.engine.keyswitch_key(to_pbs, p.big_lwe_dimension, pp.lwe_dimension,
+                                                            pp.ks_base_log, pp.ks_level))
+        key._wopbs_client_key = wcks
+        return key
 
     @classmethod
     def new_wopbs_key_only_for_wopbs(cls, cks: ClientKey, sks: ServerKey) -> "WopbsKey":
@@ -305,7 +353,9 @@ class WopbsKey:
         pfpksk = client.gen_pfpksk_list(cks.seed * 7 + 5, cks.large_lwe_secret_key, cks.glwe_secret_key,
                                         p.glwe_dimension, p.polynomial_size, p.pfks_base_log, p.pfks_level,
                                         p.pfks_modular_std_dev)
-        return cls(sks, p, pfpksk)
+        key = cls(sks, p, pfpksk)
+        key._wopbs_client_key = cks
+        return key
 
     @property
     def engine(self) -> Engine:
@@ -354,6 +404,65 @@ class WopbsKey:
         delta_log = (2 * p.delta).bit_length() - 1
         return self.extract_bits_circuit_bootstrapping(ct_in, lut, delta_log,
                                                        int(np.log2(p.message_modulus * p.carry_modulus)))
+
+
+    # -- between the PBS and the WoP parameter sets (wopbs/mod.rs:660-754); a list is one batch -------
+    @staticmethod
+    def _batch(cts):
+        single = isinstance(cts, Ciphertext)
+        return single, ([cts] if single else list(cts))
+
+    def keyswitch_to_wopbs_params(self, sks: ServerKey, ct_in):
+        """Identity PBS under the PBS set (to clean the noise), then the keyswitch PBS big key -> WoP big
+        key.  The degree is the input's (the identity LUT would set the maximum)."""
+        if self.ksk_pbs_to_wopbs is None:
+            raise ValueError("keyswitch_to_wopbs_params: a key only for wopbs has no PBS -> WoP keyswitching key "
+                             "(the reference's would be the big -> small one and its result unusable)")
+        single, batch = self._batch(ct_in)
+        clean = sks.apply_lookup_table_batch(batch, sks.generate_lookup_table(lambda x: x))
+        out = self.engine.keyswitch_with_key(self.ksk_pbs_to_wopbs, np.stack([c.ct for c in clean]))
+        res = [Ciphertext(out[i].copy(), batch[i].degree, NOISE_NOMINAL, clean[i].message_modulus,
+                          clean[i].carry_modulus, batch[i].pbs_order) for i in range(len(batch))]
+        return res[0] if single else res
+
+    def keyswitch_to_pbs_params(self, ct_in):
+        """Keyswitch WoP big key -> PBS small key, then an identity PBS under the PBS set."""
+        single, batch = self._batch(ct_in)
+        ps = self.pbs_server_key
+        x = np.stack([c.ct for c in batch])
+        if self.ksk_wopbs_to_pbs is None:
+            small = ps.engine.keyswitch(x)
+        else:
+            small = ps.engine.keyswitch_with_key(self.ksk_wopbs_to_pbs, x)
+        out = ps.engine.programmable_bootstrap(small, ps.generate_lookup_table(lambda x: x).acc)
+        res = [Ciphertext(out[i].copy(), c.degree, NOISE_NOMINAL, c.message_modulus, c.carry_modulus, c.pbs_order)
+               for i, c in enumerate(batch)]
+        return res[0] if single else res
+
+    def programmable_bootstrapping(self, sks: ServerKey, ct_in, lut):
+        """wopbs/mod.rs:398-408: to the WoP set, the WoP-PBS, back to the PBS set."""
+        return self.keyswitch_to_pbs_params(self.wopbs(self.keyswitch_to_wopbs_params(sks, ct_in), lut))
+
+    def extract_bits(self, delta_log: int, ct_in, nbits: int) -> np.ndarray:
+        """[nbits][n+1] for one ciphertext, [count][nbits][n+1] for a list, most significant bit first."""
+        single, batch = self._batch(ct_in)
+        bits = self.engine.extract_bits(np.stack([c.ct for c in batch]), delta_log, nbits)
+        return bits[0] if single else bits
+
+    def circuit_bootstrapping_vertical_packing(self, lut, bits) -> np.ndarray:
+        """lut [nout][size] (size a multiple of N), bits [count][nbits][n+1] (or [nbits][n+1]): one composed
+        call with nout outputs under one set of GGSWs; returns [count][nout][kN+1] (or [nout][kN+1])."""
+        p = self.param
+        lut = np.ascontiguousarray(lut, dtype=np.uint64)
+        if lut.ndim != 2 or lut.shape[1] % p.polynomial_size:
+            raise ValueError("circuit_bootstrapping_vertical_packing: lut must be [nout][size], size a multiple of N")
+        bits = np.ascontiguousarray(bits, dtype=np.uint64)
+        single = bits.ndim == 2
+        if single:
+            bits = bits.reshape(1, *bits.shape)
+        out = self.engine.circuit_bootstrap_vertical_packing(
+            bits, p.cbs_base_log, p.cbs_level, lut.reshape(1, lut.shape[0], -1, p.polynomial_size))
+        return out[0] if single else out
 
 
 class CompressedServerKey:
