@@ -222,6 +222,8 @@ int tfhe_mi355_bootstrap_key_convert_async(TfheMi355Context *ctx, const uint64_t
 /* Fourier BSK held by the context: device pointer and byte size, for RCCL broadcast of the
  * converted key to the other GPUs of the node. */
 int tfhe_mi355_bootstrap_key_fourier(TfheMi355Context *ctx, void **d_ptr, size_t *bytes);
+/* (On a context that holds 32-bit-torus keys this returns the Fourier form of the u32 key, same layout,
+ * for reading; _set_ready is a 64-bit call and refused there.) */
 /* Mark the Fourier BSK as valid after it was filled externally (e.g. by a broadcast into the
  * buffer returned above). */
 int tfhe_mi355_bootstrap_key_fourier_set_ready(TfheMi355Context *ctx);
@@ -601,6 +603,106 @@ int tfhe_mi355_fill_accumulator(const TfheMi355Parameters *params, const uint64_
  * acc_inout[i] += X_i and set_out[i] = X_i, X_i = rint_half_even(fr[i] * 2^64) mod 2^64. */
 int tfhe_mi355_debug_torus_from_fraction(int device, const double *fr, uint64_t *acc_inout, uint64_t *set_out,
                                          size_t n);
+
+/* ---- 32-bit torus (the reference's boolean module, tfhe/src/boolean) ----
+ * The boolean engine computes on LweCiphertextOwned<u32> under a LweKeyswitchKeyOwned<u32> and the Fourier
+ * form of a LweBootstrapKeyOwned<u32> (boolean/engine/bootstrapping.rs:17-97, 158-212).  These entry points
+ * run that arithmetic natively: u32 words, the 32-bit signed decomposer, fast_pbs_modulus_switch with
+ * Scalar::BITS = 32 and the wrapping f64 -> u32 backward conversion (x86.rs:941-947), the accumulator
+ * rounded to 32 bits after every CMUX.  Shapes (N, k, pbs_level): (512, 2, 3), (1024, 2, 2), (1024, 1, 4),
+ * (1024, 1, 3) -- the five sets of boolean/parameters/mod.rs:123-192 -- with 2 <= pbs_base_log and
+ * pbs_base_log * pbs_level <= 30; any lwe_dimension, ks_base_log * ks_level <= 30.
+ *
+ * The context is an ordinary tfhe_mi355_context_create one (message_modulus and carry_modulus are not
+ * read by these calls).  A context holds keys of ONE torus width: a _u32 upload onto a context that holds
+ * u64 keys, a u64 upload onto one that holds u32 keys, and a compute call of the other width than the
+ * context's keys all fail with rc 1 and a message.  Not available on a multi-device context (rc 1), not
+ * coalesced, no latency kernel: a host-pointer call runs directly under the context's mutex.  The _async
+ * forms follow the rules of the u64 ones: device pointers, the caller's stream, no allocation and no
+ * synchronisation inside, scratch from the caller (the *_scratch query; too little is an error).
+ * count = 0 is a no-op. */
+
+/* Standard u32 bootstrapping key [n][pbs_level][k+1][k+1][N] (host, `len` in u32 words), converted to the
+ * Fourier domain on the device: the Fourier key is bit-identical to the conversion of the key widened to
+ * u64 (word << 32), since (double)(int32_t)x 2^-32 == (double)(int64_t)((uint64_t)x << 32) 2^-64.
+ * Replaces the convert_standard_lwe_bootstrap_key_to_fourier of bootstrapping.rs:173-195. */
+int tfhe_mi355_bootstrap_key_upload_u32(TfheMi355Context *ctx, const uint32_t *bsk, size_t len);
+/* u32 keyswitching key [kN][ks_level][n+1] (host, `len` in u32 words; bootstrapping.rs:197-206). */
+int tfhe_mi355_keyswitch_key_upload_u32(TfheMi355Context *ctx, const uint32_t *ksk, size_t len);
+
+/* programmable_bootstrap_lwe_ciphertext_mem_optimized on u32 (bootstrapping.rs:284-291): lwe_in
+ * count x (n+1), lwe_out count x (kN+1), luts lut_count general GLWE accumulators of (k+1)N u32 words,
+ * lut_indexes one per ciphertext or NULL (all LUT 0). */
+int tfhe_mi355_programmable_bootstrap_u32(TfheMi355Context *ctx, const uint32_t *lwe_in, uint32_t *lwe_out,
+                                          const uint32_t *luts, size_t lut_count, const uint32_t *lut_indexes,
+                                          size_t count);
+int tfhe_mi355_programmable_bootstrap_u32_async(TfheMi355Context *ctx, const uint32_t *d_lwe_in, uint32_t *d_lwe_out,
+                                                const uint32_t *d_luts, size_t lut_count,
+                                                const uint32_t *d_lut_indexes, size_t count, void *d_scratch,
+                                                size_t scratch_bytes, void *stream);
+int tfhe_mi355_programmable_bootstrap_u32_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+/* The same blind rotation without the sample extraction: glwe_out count x (k+1)N. */
+int tfhe_mi355_blind_rotate_u32(TfheMi355Context *ctx, const uint32_t *lwe_in, uint32_t *glwe_out,
+                                const uint32_t *luts, size_t lut_count, const uint32_t *lut_indexes, size_t count);
+int tfhe_mi355_blind_rotate_u32_async(TfheMi355Context *ctx, const uint32_t *d_lwe_in, uint32_t *d_glwe_out,
+                                      const uint32_t *d_luts, size_t lut_count, const uint32_t *d_lut_indexes,
+                                      size_t count, void *d_scratch, size_t scratch_bytes, void *stream);
+int tfhe_mi355_blind_rotate_u32_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+/* keyswitch_lwe_ciphertext on u32 (bootstrapping.rs:337-341, 374-378): count x (kN+1) -> count x (n+1). */
+int tfhe_mi355_keyswitch_u32(TfheMi355Context *ctx, const uint32_t *lwe_in, uint32_t *lwe_out, size_t count);
+int tfhe_mi355_keyswitch_u32_async(TfheMi355Context *ctx, const uint32_t *d_lwe_in, uint32_t *d_lwe_out, size_t count,
+                                   void *d_scratch, size_t scratch_bytes, void *stream);
+int tfhe_mi355_keyswitch_u32_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+
+/* A mixed batch of binary gates (boolean/engine/mod.rs:607-837): item i computes
+ * s (lhs[i] + rhs[i]) + (0, ..., 0, c) mod 2^32 with (s, c) of ops[i], T = 1 << 29, F = 7 << 29
+ * (boolean/mod.rs:77-80):
+ *   0 AND (1, F)   1 NAND (-1, T)   2 NOR (-1, F)   3 OR (1, T)   4 XOR (2, 2T)   5 XNOR (-2, -2T)
+ * then apply_bootstrapping_pattern (bootstrapping.rs:392-401) with the constant-T accumulator
+ * (bootstrapping.rs:59-60): pbs_order 1 (BootstrapKeyswitch) PBS then keyswitch, rows of n+1 words in and
+ * out; pbs_order 0 (KeyswitchBootstrap) keyswitch then PBS, rows of kN+1 words.  ops: count bytes (host
+ * for the host-pointer call, which refuses an opcode above 5; device for _async, where such an item
+ * bootstraps a row of zeros). */
+#define TFHE_MI355_GATE_AND 0
+#define TFHE_MI355_GATE_NAND 1
+#define TFHE_MI355_GATE_NOR 2
+#define TFHE_MI355_GATE_OR 3
+#define TFHE_MI355_GATE_XOR 4
+#define TFHE_MI355_GATE_XNOR 5
+int tfhe_mi355_boolean_gates(TfheMi355Context *ctx, const uint8_t *ops, const uint32_t *lhs, const uint32_t *rhs,
+                             uint32_t *out, size_t count, int pbs_order);
+int tfhe_mi355_boolean_gates_async(TfheMi355Context *ctx, const uint8_t *d_ops, const uint32_t *d_lhs,
+                                   const uint32_t *d_rhs, uint32_t *d_out, size_t count, int pbs_order,
+                                   void *d_scratch, size_t scratch_bytes, void *stream);
+int tfhe_mi355_boolean_gates_scratch(TfheMi355Context *ctx, size_t count, int pbs_order, size_t *bytes);
+/* MUX of encrypted operands (mod.rs:502-566): the rows cond + then + F and -cond + else + F, ONE PBS
+ * launch over the 2 count rows, out = pbs1 + pbs2 + T; for pbs_order 1 the keyswitch comes after the
+ * sum, for pbs_order 0 before the two bootstraps. */
+int tfhe_mi355_boolean_mux(TfheMi355Context *ctx, const uint32_t *cond, const uint32_t *then_ct,
+                           const uint32_t *else_ct, uint32_t *out, size_t count, int pbs_order);
+int tfhe_mi355_boolean_mux_async(TfheMi355Context *ctx, const uint32_t *d_cond, const uint32_t *d_then,
+                                 const uint32_t *d_else, uint32_t *d_out, size_t count, int pbs_order,
+                                 void *d_scratch, size_t scratch_bytes, void *stream);
+int tfhe_mi355_boolean_mux_scratch(TfheMi355Context *ctx, size_t count, int pbs_order, size_t *bytes);
+/* NOT (mod.rs:377-398): d_out[i] = -d_in[i] for `words` u32 words on the device; no key, no PBS. */
+int tfhe_mi355_boolean_not_async(TfheMi355Context *ctx, const uint32_t *d_in, uint32_t *d_out, size_t words,
+                                 void *stream);
+
+/* Diagnostic (test hook, host buffers, synchronous): the u32 backward conversion's last step
+ * (convert_add_backward_torus_u32, x86.rs:877-947) on n fractions fr in [-1/2, 1/2]: acc_inout[i] += X_i
+ * and set_out[i] = X_i, X_i = rint_half_even(fr[i] * 2^32) mod 2^32 (fr = +-1/2 give 0x80000000). */
+int tfhe_mi355_debug_torus32_from_fraction(int device, const double *fr, uint32_t *acc_inout, uint32_t *set_out,
+                                           size_t n);
+/* Diagnostic (test hook, host buffers, synchronous): one u32 keyswitch under the caller's key
+ * [in_dim][level][out_dim+1] of its own dimensions and decomposition (base_log * level <= 30), through a
+ * chosen kernel: arm 0 the engine's choice (the int8-MFMA arm where it takes the shape), 1 the plain
+ * integer kernel, 2 the int8-MFMA kernel (rc 1 where that arm does not take the shape).  The key is
+ * uploaded, repacked and dropped within the call; the context's keys are not touched. */
+int tfhe_mi355_debug_keyswitch_u32(TfheMi355Context *ctx, const uint32_t *ksk, size_t in_dim, size_t out_dim,
+                                   uint32_t base_log, uint32_t level, int arm, const uint32_t *lwe_in,
+                                   uint32_t *lwe_out, size_t count);
+/* Diagnostic: ciphertexts (= workgroups) of the u32 PBS kernel of the context's shape resident at once. */
+int tfhe_mi355_debug_pbs_u32_resident(TfheMi355Context *ctx, size_t *count);
 
 /* ---- client-side helpers (not on the PBS path; seeded, deterministic per (seed, index)) ----
  * Binary secret keys, Gaussian noise (commons/math/random/gaussian.rs:15-52), GGSW/BSK

@@ -356,6 +356,57 @@ struct GgswCmuxLaunch {
 bool ggsw_ops_supported(int N, int k);
 hipError_t launch_ggsw_cmux(int N, int k, const GgswCmuxLaunch &a, hipStream_t s);
 
+// ---- 32-bit torus (the reference's boolean module: pbs_classic32.hip, keyswitch32.hip, boolean_ops.hip) ----
+struct ClassicPbs32Launch {
+    const uint32_t *lwe_in;      // [count][n+1]
+    uint32_t *lwe_out;           // [count][k*N+1], or [count][(k+1)N] when glwe_out
+    const uint32_t *luts;        // [lut_count][(k+1)*N]
+    const uint32_t *lut_indexes; // [count] or null; entries >= lut_count read LUT lut_count-1
+    uint32_t lut_count;
+    const double2 *fbsk;         // engine Fourier layout (of the key widened to u64)
+    const double2 *W, *twist;
+    int n;
+    int base_log;                // 2 <= base_log, base_log * L <= 30
+    int count;
+    int glwe_out;
+};
+bool classic_pbs32_supported(int N, int k, int L);
+// workgroups (= ciphertexts) of the shape's kernel resident at once on the current device
+int classic_pbs32_resident_blocks(int N, int k, int L);
+hipError_t launch_classic_pbs32(int N, int k, int L, const ClassicPbs32Launch &a, hipStream_t s);
+// out[e] = (uint64_t)in[e] << 32: the u32 standard BSK as launch_bsk_to_fourier reads it
+hipError_t launch_widen32(const uint32_t *in, uint64_t *out, size_t n, hipStream_t s);
+
+struct Keyswitch32Launch {
+    const uint32_t *lwe_in;  // [count][in_dim+1]
+    uint32_t *lwe_out;       // [count][out_dim+1]
+    const uint32_t *ksk;     // [in_dim][level][out_dim+1]
+    int in_dim, out_dim, base_log, level;  // base_log * level <= 30
+    int count;
+};
+// plain integer arm: 1 <= base_log <= 15, level <= 16
+bool keyswitch32_scalar_supported(int base_log, int level);
+hipError_t launch_keyswitch32(const Keyswitch32Launch &a, hipStream_t s);
+// int8-MFMA arm: KSK repacked once into 4 byte planes (ks_mfma_cols x ks_mfma_rows each)
+bool ks32_mfma_supported(int in_dim, int level, int base_log);
+size_t ks32_mfma_scratch_bytes(int in_dim, int level, int count);
+hipError_t launch_ksk32_repack(const uint32_t *ksk, int8_t *kt, int in_dim, int level, int out_dim, hipStream_t s);
+hipError_t launch_keyswitch32_mfma(const Keyswitch32Launch &a, const int8_t *kt, void *scratch, hipStream_t s);
+
+// linear parts of the boolean gates (boolean_ops.hip; boolean/engine/mod.rs:461-837), mod 2^32:
+//   gates:        out[i] = s(op[i]) (lhs[i] + rhs[i]) + (0, ..., 0, c(op[i]))
+//   mux prologue: out[2i] = cond[i] + then[i] + (0.., F), out[2i+1] = -cond[i] + else[i] + (0.., F)
+//   mux epilogue: out[i] = in[2i] + in[2i+1] + (0.., T)
+//   negate:       out[i] = -in[i]
+// an opcode above 5 (refused by the host-pointer entry point) writes a row of zeros
+hipError_t launch_bool_gates_prologue(const uint8_t *ops, const uint32_t *lhs, const uint32_t *rhs, uint32_t *out,
+                                      size_t count, size_t words, hipStream_t s);
+hipError_t launch_bool_mux_prologue(const uint32_t *cond, const uint32_t *then_, const uint32_t *else_, uint32_t *out,
+                                    size_t count, size_t words, hipStream_t s);
+hipError_t launch_bool_mux_epilogue(const uint32_t *in, uint32_t *out, size_t count, size_t words, hipStream_t s);
+hipError_t launch_bool_negate(const uint32_t *in, uint32_t *out, size_t total, hipStream_t s);
+hipError_t launch_torus32_from_fraction(const double *fr, uint32_t *acc, uint32_t *set, size_t n, hipStream_t s);
+
 // seeded-key decompression (csprng.hip): AES-CTR mask stream of the compression seed written as
 // `row_words` mask words per row, followed by `body_words` copied from d_bodies, for `rows` rows
 size_t aes_tables_bytes();

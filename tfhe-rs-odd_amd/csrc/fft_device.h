@@ -830,4 +830,22 @@ __device__ __forceinline__ void backward_sub(cx z, cx ws, uint64_t &c_re, uint64
     torus_add_frac(c_im, rint(mi) - mi, k32);
 }
 
+// ---- 32-bit torus (pbs_classic32.hip, boolean_ops.hip) ----
+// c += rint(fr 2^32) mod 2^32 for fr in [-1/2, 1/2].  fma(fr, 2^32, 1.5 2^52) is 1.5 2^52 +
+// rint_half_even(fr 2^32) (ulp 1 there, fr 2^32 exact), its bit pattern 0x4338000000000000 + that
+// integer: the low word is the increment mod 2^32, so fr = +-1/2 both give 0x80000000 (the
+// reference's _mm256_cvtpd_epi32 wraps the same way; a saturating convert would give 0x7fffffff).
+__device__ __forceinline__ uint32_t torus32_from_frac(double fr) {
+    return (uint32_t)__double2loint(fma(fr, 0x1p32, TORUS_MB));
+}
+
+// backward conversion, added in place: c_re += increment(j), c_im += increment(j + M); t as
+// backward_add (fft_device.h) computes it
+__device__ __forceinline__ void backward_add32(cx z, cx ws, uint32_t &c_re, uint32_t &c_im) {
+    double mr = fma(z.re, ws.re, z.im * ws.im);
+    double mi = fma(-z.re, ws.im, z.im * ws.re);
+    c_re += torus32_from_frac(mr - rint(mr));
+    c_im += torus32_from_frac(mi - rint(mi));
+}
+
 }  // namespace tfhe_mi355

@@ -195,6 +195,30 @@ SIGNATURES = [
     ("tfhe_mi355_coalesce_stats", ctypes.c_int,
      [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+    # 32-bit torus (the reference's boolean module)
+    ("tfhe_mi355_bootstrap_key_upload_u32", ctypes.c_int, [vp, u32p, sz]),
+    ("tfhe_mi355_keyswitch_key_upload_u32", ctypes.c_int, [vp, u32p, sz]),
+    ("tfhe_mi355_programmable_bootstrap_u32", ctypes.c_int, [vp, u32p, u32p, u32p, sz, u32p, sz]),
+    ("tfhe_mi355_programmable_bootstrap_u32_async", ctypes.c_int, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_programmable_bootstrap_u32_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_blind_rotate_u32", ctypes.c_int, [vp, u32p, u32p, u32p, sz, u32p, sz]),
+    ("tfhe_mi355_blind_rotate_u32_async", ctypes.c_int, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_blind_rotate_u32_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_keyswitch_u32", ctypes.c_int, [vp, u32p, u32p, sz]),
+    ("tfhe_mi355_keyswitch_u32_async", ctypes.c_int, [vp, vp, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_keyswitch_u32_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_boolean_gates", ctypes.c_int, [vp, u8p, u32p, u32p, u32p, sz, ctypes.c_int]),
+    ("tfhe_mi355_boolean_gates_async", ctypes.c_int, [vp, vp, vp, vp, vp, sz, ctypes.c_int, vp, sz, vp]),
+    ("tfhe_mi355_boolean_gates_scratch", ctypes.c_int, [vp, sz, ctypes.c_int, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_boolean_mux", ctypes.c_int, [vp, u32p, u32p, u32p, u32p, sz, ctypes.c_int]),
+    ("tfhe_mi355_boolean_mux_async", ctypes.c_int, [vp, vp, vp, vp, vp, sz, ctypes.c_int, vp, sz, vp]),
+    ("tfhe_mi355_boolean_mux_scratch", ctypes.c_int, [vp, sz, ctypes.c_int, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_boolean_not_async", ctypes.c_int, [vp, vp, vp, sz, vp]),
+    ("tfhe_mi355_debug_torus32_from_fraction", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(ctypes.c_double), u32p, u32p, sz]),
+    ("tfhe_mi355_debug_keyswitch_u32", ctypes.c_int,
+     [vp, u32p, sz, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, u32p, u32p, sz]),
+    ("tfhe_mi355_debug_pbs_u32_resident", ctypes.c_int, [vp, ctypes.POINTER(sz)]),
 ]
 
 _lib = None

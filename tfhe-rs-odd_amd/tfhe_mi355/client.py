@@ -171,3 +171,26 @@ def decode(plaintexts, delta: int) -> np.ndarray:
     rb = np.uint64(delta >> 1)
     rounding = (d & rb) << np.uint64(1)
     return (d + rounding) // np.uint64(delta)
+
+
+# ---- 32-bit torus (boolean module) -------------------------------------------------------------------
+def round_to_u32(words64) -> np.ndarray:
+    """The top 32 bits of u64 torus words, rounded: (x + 2^31) >> 32 mod 2^32.  The boolean helpers
+    derive u32 keys and ciphertexts from the u64 generators this way; the rounding adds a uniform
+    error of at most 2^-33 to each word, below every boolean set's noise (>= 2^-30)."""
+    x = np.ascontiguousarray(words64, dtype=np.uint64)
+    return ((x + np.uint64(1 << 31)) >> np.uint64(32)).astype(np.uint32)
+
+
+def lwe_encrypt_u32(seed, sk, plaintexts32, std_dev) -> np.ndarray:
+    """u32 LWE encryptions [count][len(sk)+1] of u32 plaintexts (u64 encryption of pt << 32, rounded)."""
+    pts = np.ascontiguousarray(plaintexts32, dtype=np.uint64).ravel() << np.uint64(32)
+    return round_to_u32(lwe_encrypt(seed, sk, pts, std_dev))
+
+
+def lwe_decrypt_u32(sk, cts32) -> np.ndarray:
+    """Phases body - <mask, sk> mod 2^32 of u32 LWE ciphertexts."""
+    sk = np.ascontiguousarray(sk, dtype=np.uint64)
+    c = np.ascontiguousarray(cts32, dtype=np.uint32).reshape(-1, len(sk) + 1).astype(np.uint64)
+    dot = (c[:, :-1] * sk[None, :]).sum(axis=1, dtype=np.uint64)
+    return ((c[:, -1] - dot) & np.uint64(0xFFFFFFFF)).astype(np.uint32)

@@ -21,6 +21,14 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(u64p)
 
 
+def _u32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _ptr32(a: np.ndarray):
+    return a.ctypes.data_as(u32p)
+
+
 def _dev_ptr(t) -> int:
     """Device pointer of a torch tensor (or a raw int)."""
     if t is None:
@@ -607,6 +615,143 @@ class Engine:
     # Every device scratch the C ABI needs comes from the caller (include/tfhe_mi355.h): pass
     # d_scratch (>= the matching *_scratch_bytes), or let these wrappers allocate it from torch's
     # caching allocator for the call.
+    # -- 32-bit torus (the reference's boolean module; include/tfhe_mi355.h "32-bit torus") ------------
+    # Host arrays are uint32; device tensors are torch.int32 (same bits).  A context holds keys of one
+    # torus width; these calls are single-device.
+    def upload_bootstrap_key_u32(self, standard_bsk) -> None:
+        b = _u32(standard_bsk).ravel()
+        _lib.call("tfhe_mi355_bootstrap_key_upload_u32", self._h, _ptr32(b), b.size)
+
+    def upload_keyswitch_key_u32(self, ksk) -> None:
+        k = _u32(ksk).ravel()
+        _lib.call("tfhe_mi355_keyswitch_key_upload_u32", self._h, _ptr32(k), k.size)
+
+    def _luts32(self, luts):
+        luts = _u32(luts)
+        if luts.ndim == 1:
+            luts = luts.reshape(1, -1)
+        if luts.shape[1] != self.glwe_len:
+            raise ValueError(f"lookup table has {luts.shape[1]} words, expected {self.glwe_len}")
+        return luts
+
+    def programmable_bootstrap_u32(self, lwe_in, luts, lut_indexes=None) -> np.ndarray:
+        x = _u32(lwe_in).reshape(-1, self.n + 1)
+        L = self._luts32(luts)
+        idx, idxp = self._idx(lut_indexes, x.shape[0], L.shape[0])
+        out = np.empty((x.shape[0], self.big_dim + 1), dtype=np.uint32)
+        _lib.call("tfhe_mi355_programmable_bootstrap_u32", self._h, _ptr32(x), _ptr32(out), _ptr32(L), L.shape[0],
+                  idxp, x.shape[0])
+        return out
+
+    def blind_rotate_u32(self, lwe_in, luts, lut_indexes=None) -> np.ndarray:
+        x = _u32(lwe_in).reshape(-1, self.n + 1)
+        L = self._luts32(luts)
+        idx, idxp = self._idx(lut_indexes, x.shape[0], L.shape[0])
+        out = np.empty((x.shape[0], self.glwe_len), dtype=np.uint32)
+        _lib.call("tfhe_mi355_blind_rotate_u32", self._h, _ptr32(x), _ptr32(out), _ptr32(L), L.shape[0], idxp,
+                  x.shape[0])
+        return out
+
+    def keyswitch_u32(self, lwe_in) -> np.ndarray:
+        x = _u32(lwe_in).reshape(-1, self.big_dim + 1)
+        out = np.empty((x.shape[0], self.n + 1), dtype=np.uint32)
+        _lib.call("tfhe_mi355_keyswitch_u32", self._h, _ptr32(x), _ptr32(out), x.shape[0])
+        return out
+
+    def gate_words(self, pbs_order: int) -> int:
+        """Words per ciphertext row of a gate call: n+1 for pbs_order 1 (BootstrapKeyswitch), kN+1 for 0."""
+        return (self.n if pbs_order else self.big_dim) + 1
+
+    def boolean_gates(self, ops, lhs, rhs, pbs_order: int) -> np.ndarray:
+        """A mixed batch of binary gates (opcodes 0 AND, 1 NAND, 2 NOR, 3 OR, 4 XOR, 5 XNOR)."""
+        w = self.gate_words(pbs_order)
+        a, b = _u32(lhs).reshape(-1, w), _u32(rhs).reshape(-1, w)
+        o = np.ascontiguousarray(ops, dtype=np.uint8).ravel()
+        if a.shape != b.shape or o.size != a.shape[0]:
+            raise ValueError("ops, lhs and rhs must have one entry per gate")
+        out = np.empty_like(a)
+        _lib.call("tfhe_mi355_boolean_gates", self._h, o.ctypes.data_as(_lib.u8p), _ptr32(a), _ptr32(b), _ptr32(out),
+                  a.shape[0], int(pbs_order))
+        return out
+
+    def boolean_mux(self, cond, then_ct, else_ct, pbs_order: int) -> np.ndarray:
+        w = self.gate_words(pbs_order)
+        c, t, e = (_u32(x).reshape(-1, w) for x in (cond, then_ct, else_ct))
+        if not (c.shape == t.shape == e.shape):
+            raise ValueError("cond, then and else must have the same shape")
+        out = np.empty_like(c)
+        _lib.call("tfhe_mi355_boolean_mux", self._h, _ptr32(c), _ptr32(t), _ptr32(e), _ptr32(out), c.shape[0],
+                  int(pbs_order))
+        return out
+
+    def boolean_not(self, ct) -> np.ndarray:
+        """NOT negates every word (boolean/engine/mod.rs:377-398); host arrays need no kernel."""
+        return (np.uint32(0) - _u32(ct)).astype(np.uint32)
+
+    def _scratch_query_order(self, fn: str, count: int, pbs_order: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call(fn, self._h, count, int(pbs_order), ctypes.byref(b))
+        return b.value
+
+    def pbs_u32_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_programmable_bootstrap_u32_scratch", count)
+
+    def ks_u32_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_keyswitch_u32_scratch", count)
+
+    def boolean_gates_scratch_bytes(self, count: int, pbs_order: int) -> int:
+        return self._scratch_query_order("tfhe_mi355_boolean_gates_scratch", count, pbs_order)
+
+    def boolean_mux_scratch_bytes(self, count: int, pbs_order: int) -> int:
+        return self._scratch_query_order("tfhe_mi355_boolean_mux_scratch", count, pbs_order)
+
+    def programmable_bootstrap_u32_async(self, d_in, d_out, d_luts, lut_count: int, count: int, d_lut_indexes=None,
+                                         stream=None, d_scratch=None, glwe_out: bool = False) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.pbs_u32_scratch_bytes(count), stream)
+        fn = "tfhe_mi355_blind_rotate_u32_async" if glwe_out else "tfhe_mi355_programmable_bootstrap_u32_async"
+        _lib.call(fn, self._h, _dev_ptr(d_in), _dev_ptr(d_out), _dev_ptr(d_luts), lut_count,
+                  _dev_ptr(d_lut_indexes), count, sp, sb, _stream_ptr(stream))
+
+    def keyswitch_u32_async(self, d_in, d_out, count: int, stream=None, d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.ks_u32_scratch_bytes(count), stream)
+        _lib.call("tfhe_mi355_keyswitch_u32_async", self._h, _dev_ptr(d_in), _dev_ptr(d_out), count, sp, sb,
+                  _stream_ptr(stream))
+
+    def boolean_gates_async(self, d_ops, d_lhs, d_rhs, d_out, count: int, pbs_order: int, stream=None,
+                            d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.boolean_gates_scratch_bytes(count, pbs_order), stream)
+        _lib.call("tfhe_mi355_boolean_gates_async", self._h, _dev_ptr(d_ops), _dev_ptr(d_lhs), _dev_ptr(d_rhs),
+                  _dev_ptr(d_out), count, int(pbs_order), sp, sb, _stream_ptr(stream))
+
+    def boolean_mux_async(self, d_cond, d_then, d_else, d_out, count: int, pbs_order: int, stream=None,
+                          d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.boolean_mux_scratch_bytes(count, pbs_order), stream)
+        _lib.call("tfhe_mi355_boolean_mux_async", self._h, _dev_ptr(d_cond), _dev_ptr(d_then), _dev_ptr(d_else),
+                  _dev_ptr(d_out), count, int(pbs_order), sp, sb, _stream_ptr(stream))
+
+    def boolean_not_async(self, d_in, d_out, words: int, stream=None) -> None:
+        _lib.call("tfhe_mi355_boolean_not_async", self._h, _dev_ptr(d_in), _dev_ptr(d_out), words,
+                  _stream_ptr(stream))
+
+    def debug_keyswitch_u32(self, ksk, in_dim: int, out_dim: int, base_log: int, level: int, lwe_in,
+                            arm: int = 0) -> np.ndarray:
+        """One u32 keyswitch under `ksk` [in_dim][level][out_dim+1] through kernel `arm` (0 the engine's choice,
+        1 integer, 2 int8 MFMA); a test hook, the context's keys are not touched."""
+        k = _u32(ksk).ravel()
+        if k.size != in_dim * level * (out_dim + 1):
+            raise ValueError("keyswitching key size")
+        x = _u32(lwe_in).reshape(-1, in_dim + 1)
+        out = np.empty((x.shape[0], out_dim + 1), dtype=np.uint32)
+        _lib.call("tfhe_mi355_debug_keyswitch_u32", self._h, _ptr32(k), in_dim, out_dim, base_log, level, arm,
+                  _ptr32(x), _ptr32(out), x.shape[0])
+        return out
+
+    def pbs_u32_resident(self) -> int:
+        """Ciphertexts (= workgroups) of the u32 PBS kernel resident at once on the device."""
+        n = sz()
+        _lib.call("tfhe_mi355_debug_pbs_u32_resident", self._h, ctypes.byref(n))
+        return n.value
+
     def _scratch_query(self, fn: str, count: int) -> int:
         b = ctypes.c_size_t()
         _lib.call(fn, self._h, count, ctypes.byref(b))
@@ -728,6 +873,16 @@ class Engine:
         _lib.call("tfhe_mi355_vertical_packing_async", self._h, _dev_ptr(d_fourier), base_log, level, nbits,
                   _dev_ptr(d_luts), lut_count, npoly, _dev_ptr(d_lut_indexes), count, _dev_ptr(d_out), sp, sb,
                   _stream_ptr(stream))
+
+
+def debug_torus32_from_fraction(fr, acc=None, device: int = 0):
+    """(acc + X, X) with X = rint_half_even(fr * 2^32) mod 2^32, computed by the u32 PBS kernel's conversion."""
+    f = np.ascontiguousarray(fr, dtype=np.float64).ravel()
+    a = np.zeros(f.size, dtype=np.uint32) if acc is None else _u32(acc).ravel().copy()
+    x = np.empty(f.size, dtype=np.uint32)
+    _lib.call("tfhe_mi355_debug_torus32_from_fraction", device, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+              _ptr32(a), _ptr32(x), f.size)
+    return a, x
 
 
 def fill_accumulator(params: ClassicPBSParameters, f) -> np.ndarray:

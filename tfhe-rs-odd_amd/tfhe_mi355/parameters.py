@@ -11,6 +11,7 @@ authoritative -- see SURVEY.md 0.4 for the BASELINE.json annotation mismatch).
   GADGET_* (fork)                  gadget/parameters/mod.rs:84-222 (DEFAULT, SIMON_40,
                                    ZAMA_TRIVIUM, ASCON_40, SHA3_40, AES_40, AES_23, TFHE_LIB)
   TEST_PARAMS_4_BITS_NATIVE_U64    core_crypto/algorithms/test/mod.rs:56-73
+  BOOLEAN_* (32-bit torus)         boolean/parameters/mod.rs:123-192 (the five BooleanParameters sets)
 """
 from __future__ import annotations
 
@@ -284,3 +285,69 @@ WOPBS_PARAM_MESSAGE_2_CARRY_2_KS_PBS = WopbsParameters(
     cbs_base_log=5, cbs_level=3, name="WOPBS_PARAM_MESSAGE_2_CARRY_2_KS_PBS")
 WOPBS_ALL = {p.name: p for p in [WOPBS_PARAM_MESSAGE_1_CARRY_1_KS_PBS, WOPBS_PARAM_MESSAGE_1_CARRY_2_KS_PBS,
                                  WOPBS_PARAM_MESSAGE_2_CARRY_2_KS_PBS]}
+
+
+# ---- boolean module (32-bit torus) -----------------------------------------------------------------
+@dataclass(frozen=True)
+class BooleanParameters:
+    """Mirror of BooleanParameters (boolean/parameters/mod.rs:34-64).  The ciphertext words are u32;
+    encryption_key_choice "Small" = PBSOrder::BootstrapKeyswitch, "Big" = PBSOrder::KeyswitchBootstrap."""
+
+    lwe_dimension: int
+    glwe_dimension: int
+    polynomial_size: int
+    lwe_modular_std_dev: float
+    glwe_modular_std_dev: float
+    pbs_base_log: int
+    pbs_level: int
+    ks_base_log: int
+    ks_level: int
+    encryption_key_choice: str
+    name: str = ""
+    # fields the engine's context reads from every parameter set; the 32-bit calls ignore the moduli
+    message_modulus: int = 2
+    carry_modulus: int = 1
+    grouping_factor: int = 0
+
+    @property
+    def big_lwe_dimension(self) -> int:
+        return self.glwe_dimension * self.polynomial_size
+
+    @property
+    def pbs_order(self) -> int:
+        """1 = BootstrapKeyswitch (ciphertexts under the small key), 0 = KeyswitchBootstrap."""
+        return 1 if self.encryption_key_choice == "Small" else 0
+
+    @property
+    def ciphertext_words(self) -> int:
+        return (self.lwe_dimension if self.pbs_order else self.big_lwe_dimension) + 1
+
+
+BOOLEAN_DEFAULT_PARAMETERS = BooleanParameters(
+    lwe_dimension=722, glwe_dimension=2, polynomial_size=512,
+    lwe_modular_std_dev=0.000013071021089943935, glwe_modular_std_dev=0.00000004990272175010415,
+    pbs_base_log=6, pbs_level=3, ks_base_log=3, ks_level=4,
+    encryption_key_choice="Small", name="DEFAULT_PARAMETERS")
+BOOLEAN_DEFAULT_PARAMETERS_KS_PBS = BooleanParameters(
+    lwe_dimension=664, glwe_dimension=2, polynomial_size=512,
+    lwe_modular_std_dev=0.00003808282923459771, glwe_modular_std_dev=0.00000004990272175010415,
+    pbs_base_log=6, pbs_level=3, ks_base_log=3, ks_level=4,
+    encryption_key_choice="Big", name="DEFAULT_PARAMETERS_KS_PBS")
+BOOLEAN_PARAMETERS_ERROR_PROB_2_POW_MINUS_165 = BooleanParameters(
+    lwe_dimension=767, glwe_dimension=2, polynomial_size=1024,
+    lwe_modular_std_dev=0.000005104350373791501, glwe_modular_std_dev=0.0000000009313225746154785,
+    pbs_base_log=10, pbs_level=2, ks_base_log=3, ks_level=5,
+    encryption_key_choice="Small", name="PARAMETERS_ERROR_PROB_2_POW_MINUS_165")
+BOOLEAN_PARAMETERS_ERROR_PROB_2_POW_MINUS_165_KS_PBS = BooleanParameters(
+    lwe_dimension=700, glwe_dimension=1, polynomial_size=1024,
+    lwe_modular_std_dev=0.0000196095987892077, glwe_modular_std_dev=0.00000004990272175010415,
+    pbs_base_log=5, pbs_level=4, ks_base_log=2, ks_level=7,
+    encryption_key_choice="Big", name="PARAMETERS_ERROR_PROB_2_POW_MINUS_165_KS_PBS")
+BOOLEAN_TFHE_LIB_PARAMETERS = BooleanParameters(
+    lwe_dimension=630, glwe_dimension=1, polynomial_size=1024,
+    lwe_modular_std_dev=0.000030517578125, glwe_modular_std_dev=0.00000002980232238769531,
+    pbs_base_log=7, pbs_level=3, ks_base_log=2, ks_level=8,
+    encryption_key_choice="Small", name="TFHE_LIB_PARAMETERS")
+BOOLEAN_PARAMETER_SETS = (
+    BOOLEAN_DEFAULT_PARAMETERS, BOOLEAN_DEFAULT_PARAMETERS_KS_PBS, BOOLEAN_PARAMETERS_ERROR_PROB_2_POW_MINUS_165,
+    BOOLEAN_PARAMETERS_ERROR_PROB_2_POW_MINUS_165_KS_PBS, BOOLEAN_TFHE_LIB_PARAMETERS)
