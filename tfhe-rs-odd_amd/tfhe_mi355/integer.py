@@ -34,7 +34,9 @@ numpy array on the host -- same DAG, same bits.
 
 Carry propagation uses the Hillis-Steele branch; the reference selects it whenever
 should_hillis_steele_propagation_be_faster (add.rs:44-76) holds, i.e. with >= 16 rayon threads
-for 16 blocks.
+for 16 blocks.  The reference's sequential branch is not implemented: on a modulus pair the Hillis-Steele
+branch and the chunked sum cannot serve (propagation_refusal, mul_refusal) the carry-propagating entry
+points raise NotImplementedError before any PBS.
 """
 from __future__ import annotations
 
@@ -304,6 +306,42 @@ class _DeviceOps:
         return n
 
 
+def propagation_refusal(msg: int, carry: int):
+    """Why the Hillis-Steele carry propagation and the chunked sum cannot serve a modulus pair (None: they
+    can).  The reference takes this branch only with 4 bits per block
+    (is_eligible_for_parallel_single_carry_propagation, add.rs:448-462) and propagates block by block
+    otherwise; that sequential branch is not implemented here.  The other conditions are the ones the
+    branch's own arithmetic needs, each stated where it is used below."""
+    total = msg * carry
+    if msg < 2 or (total - 1) // (msg - 1) < 3:
+        # unchecked_sum_ciphertexts_vec: a chunk of `fill` terms becomes 2 terms (message, carry), so with
+        # fill < 3 the term list never gets shorter
+        return "fewer than 3 full messages fit in a block, so the chunked sum of terms would never shrink"
+    if total < 16:
+        return ("message_modulus * carry_modulus < 16: the reference propagates carries sequentially here "
+                "(add.rs:448-462), and only the Hillis-Steele branch is implemented")
+    if OUTPUT_CARRY_PROPAGATED + 1 > msg:
+        # _bivariate(lut_prefix): the right operand is a carry state (0, 1 or 2) in the message bits
+        return "a carry state (0, 1, 2) does not fit in the message bits of the prefix-sum bivariate PBS"
+    if OUTPUT_CARRY_PROPAGATED * msg + OUTPUT_CARRY_PROPAGATED >= total:
+        # _bivariate(lut_prefix): left carry state * message_modulus + right carry state
+        return "two carry states packed for the prefix-sum bivariate PBS overflow the block"
+    if (carry - 1) + (msg - 1) >= 2 * msg:
+        # full_propagate / the sum's last step: extracted carries (degree carry_modulus - 1) are added to
+        # extracted messages, and the single-carry propagation takes degrees below 2 * message_modulus
+        return ("carry_modulus > message_modulus: an extracted carry added to a message can exceed one carry "
+                "bit, which the single-carry propagation does not take")
+    return None
+
+
+def mul_refusal(msg: int, carry: int):
+    """Why unchecked_mul cannot serve a pair the propagation can: the bivariate product PBS packs two full
+    messages, lhs * message_modulus + rhs, into one block."""
+    if (msg - 1) * msg + (msg - 1) >= msg * carry:
+        return "carry_modulus < message_modulus: two messages packed for the bivariate product PBS overflow the block"
+    return None
+
+
 class ServerKey:
     """integer ServerKey (integer/server_key/mod.rs) over a shortint ServerKey with the GPU engine."""
 
@@ -331,6 +369,15 @@ class ServerKey:
                                                              else OUTPUT_CARRY_NONE))
         self.lut_prefix = self.generate_lookup_table_bivariate(
             lambda msb, lsb: lsb if msb == OUTPUT_CARRY_PROPAGATED else msb)
+        self.propagation_refusal = propagation_refusal(m, self.carry)
+        self.mul_refusal = self.propagation_refusal or mul_refusal(m, self.carry)
+
+    def _require(self, op: str, refusal):
+        """The carry-propagating entry points refuse a parameter set they cannot serve before the
+        first PBS or kernel launch (the key itself is built for every set: the WoP-PBS layer uses one)."""
+        if refusal:
+            raise NotImplementedError(f"integer {op}: {self.p.name or 'parameters'} (message modulus {self.msg}, "
+                                      f"carry modulus {self.carry}) is not supported: {refusal}")
 
     # -- lookup tables -----------------------------------------------------------------------
     def generate_lookup_table_bivariate(self, f) -> LookupTable:
@@ -431,6 +478,7 @@ class ServerKey:
 
     def full_propagate(self, ct: RadixBatch):
         """full_propagate_parallelized = partial_propagate_parallelized(ct, 0) (mod.rs:88-155)."""
+        self._require("full_propagate", self.propagation_refusal)
         nb = ct.num_blocks
         carries = ct.clone()
         layer = _PbsLayer(self)
@@ -447,6 +495,7 @@ class ServerKey:
 
     def add_assign_parallelized(self, lhs: RadixBatch, rhs: RadixBatch):
         """add.rs:206-242 (Hillis-Steele branch)."""
+        self._require("add_assign_parallelized", self.propagation_refusal)
         if not rhs.block_carries_are_empty(self.msg):
             rhs = rhs.clone()
             self.full_propagate(rhs)
@@ -457,6 +506,7 @@ class ServerKey:
     # -- sum of terms ------------------------------------------------------------------------
     def unchecked_sum_ciphertexts_vec(self, cts: list) -> RadixBatch | None:
         """unchecked_sum_ciphertexts_vec_parallelized (add.rs:783-960)."""
+        self._require("unchecked_sum_ciphertexts_vec", self.propagation_refusal)
         if not cts:
             return None
         if len(cts) == 1:
@@ -536,6 +586,7 @@ class ServerKey:
     # -- multiplication ------------------------------------------------------------------------
     def unchecked_mul(self, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
         """unchecked_mul_assign_parallelized (mul.rs:300-414)."""
+        self._require("unchecked_mul", self.mul_refusal)
         lhs, rhs = self._resident(lhs), self._resident(rhs)
         if rhs.holds_boolean_value() or lhs.holds_boolean_value():
             raise NotImplementedError("boolean-valued operand (zero_out_if_condition_is_false path)")
@@ -567,6 +618,7 @@ class ServerKey:
 
     def mul_parallelized(self, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
         """mul.rs:553-590."""
+        self._require("mul_parallelized", self.mul_refusal)
         lhs, rhs = self._resident(lhs), self._resident(rhs)
         lhs = lhs.clone()
         if not rhs.block_carries_are_empty(self.msg):
