@@ -704,6 +704,67 @@ int tfhe_mi355_debug_keyswitch_u32(TfheMi355Context *ctx, const uint32_t *ksk, s
 /* Diagnostic: ciphertexts (= workgroups) of the u32 PBS kernel of the context's shape resident at once. */
 int tfhe_mi355_debug_pbs_u32_resident(TfheMi355Context *ctx, size_t *count);
 
+/* ---- 128-bit torus (the reference's fft128 path, tfhe/src/core_crypto/fft_impl/fft128) ----
+ * programmable_bootstrap_f128_lwe_ciphertext (algorithms/lwe_programmable_bootstrapping.rs:1378-1459) over
+ * the Fourier form made by convert_standard_lwe_bootstrap_key_to_fourier_128
+ * (algorithms/lwe_bootstrap_key_conversion.rs:164): LweCiphertext<u128>, the 128-bit signed decomposer,
+ * fast_pbs_modulus_switch with Scalar::BITS = 128, a negacyclic FFT in double-double arithmetic and the
+ * wrapping f128 -> u128 backward conversion (fft128/math/fft/mod.rs:201-328).  The transform's operation
+ * order is this engine's own (the reference's butterflies are concrete-fft's).
+ *
+ * A u128 word is two little-endian uint64_t (low, high); every length and row size below is in u128 words.
+ * Shapes: polynomial_size in {256, 512, 1024, 2048}, glwe_dimension in {1, 2, 3} with (k+1) N <= 4096,
+ * 1 <= pbs_level <= 4, 2 <= pbs_base_log <= 31, pbs_base_log * pbs_level < 128, any lwe_dimension >= 1;
+ * ciphertext_modulus_log m in [65, 128], 128 = the native modulus; for m < 128 every accumulator word is
+ * rounded to its m most significant bits after the last CMUX (fft128/crypto/bootstrap.rs:321-334).
+ * Everything else fails with rc 1 and a message naming the limit.
+ *
+ * tfhe_mi355_context_create_u128 validates the parameters against these limits instead of the u64
+ * kernels' (the ks_* and *_modulus fields are not read); such a context serves the _u128 calls only.  An
+ * ordinary context whose shape is also within these limits takes a u128 key too.  A context holds keys of
+ * ONE torus width: a _u128 upload onto a context that holds u64 or u32 keys, a u64 or u32 upload onto one
+ * that holds a u128 key, and a compute call of another width than the context's keys all fail with rc 1.
+ * Single-device only (a multi-device context is refused, rc 1), not coalesced, no keyswitch.  The _async
+ * forms take device pointers (16-byte aligned) and the caller's stream, allocate nothing and do not
+ * synchronise; scratch comes from the caller (the *_scratch query; too little is an error).  count = 0 is a
+ * no-op. */
+int tfhe_mi355_context_create_u128(const TfheMi355Parameters *params, int device, TfheMi355Context **out_ctx);
+/* Standard u128 bootstrapping key [n][pbs_level][k+1][k+1][N] (host), converted on the device to four f64
+ * planes (re.hi, re.lo, im.hi, im.lo) of N/2 entries per polynomial, in the transform's output order. */
+int tfhe_mi355_bootstrap_key_upload_u128(TfheMi355Context *ctx, const uint64_t *bsk, size_t len);
+/* lwe_in count x (n+1), lwe_out count x (kN+1), luts lut_count general GLWE accumulators of (k+1)N words,
+ * lut_indexes one per ciphertext or NULL (all LUT 0). */
+int tfhe_mi355_programmable_bootstrap_u128(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *lwe_out,
+                                           const uint64_t *luts, size_t lut_count, const uint32_t *lut_indexes,
+                                           size_t count, uint32_t ciphertext_modulus_log);
+int tfhe_mi355_programmable_bootstrap_u128_async(TfheMi355Context *ctx, const uint64_t *d_lwe_in, uint64_t *d_lwe_out,
+                                                 const uint64_t *d_luts, size_t lut_count,
+                                                 const uint32_t *d_lut_indexes, size_t count,
+                                                 uint32_t ciphertext_modulus_log, void *d_scratch,
+                                                 size_t scratch_bytes, void *stream);
+int tfhe_mi355_programmable_bootstrap_u128_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+/* The same blind rotation without the sample extraction: glwe_out count x (k+1)N
+ * (Fourier128LweBootstrapKey::blind_rotate_assign, bootstrap.rs:245-337). */
+int tfhe_mi355_blind_rotate_u128(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *glwe_out,
+                                 const uint64_t *luts, size_t lut_count, const uint32_t *lut_indexes, size_t count,
+                                 uint32_t ciphertext_modulus_log);
+int tfhe_mi355_blind_rotate_u128_async(TfheMi355Context *ctx, const uint64_t *d_lwe_in, uint64_t *d_glwe_out,
+                                       const uint64_t *d_luts, size_t lut_count, const uint32_t *d_lut_indexes,
+                                       size_t count, uint32_t ciphertext_modulus_log, void *d_scratch,
+                                       size_t scratch_bytes, void *stream);
+int tfhe_mi355_blind_rotate_u128_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes);
+/* Diagnostic (host only, no GPU): the canonical double-double tables of the f128 FFT.  twist: 4 planes of
+ * N/2 doubles (cos.hi, cos.lo, sin.hi, sin.lo of pi j / N); twiddles: 4 planes of N/4 doubles
+ * (exp(-2 pi i t / (N/2))).  Every entry is hi = RN(x), lo = RN(x - hi) of the exact real x. */
+int tfhe_mi355_debug_fft128_tables(uint32_t polynomial_size, double *twist, double *twiddles);
+/* Diagnostic (test hook, host buffers, synchronous): the f128 kernel's backward conversion alone
+ * (u128_from_torus_f128, mod.rs:226-239), one thread per value: out[i] = acc[i] + X_i (acc may be NULL),
+ * X_i = floor((x - floor x) 2^128 + 1/2) mod 2^128 of the double-double x = hi[i] + lo[i]. */
+int tfhe_mi355_debug_torus128_from_f128(int device, const double *hi, const double *lo, const uint64_t *acc,
+                                        uint64_t *out, size_t count);
+/* Diagnostic: ciphertexts (= workgroups) of the f128 PBS kernel of the context's shape resident at once. */
+int tfhe_mi355_debug_pbs_u128_resident(TfheMi355Context *ctx, size_t *count);
+
 /* ---- client-side helpers (not on the PBS path; seeded, deterministic per (seed, index)) ----
  * Binary secret keys, Gaussian noise (commons/math/random/gaussian.rs:15-52), GGSW/BSK
  * (ggsw_encryption.rs:116-150,300-331), KSK (lwe_keyswitch_key_generation.rs:60-135),

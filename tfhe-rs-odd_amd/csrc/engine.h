@@ -407,6 +407,38 @@ hipError_t launch_bool_mux_epilogue(const uint32_t *in, uint32_t *out, size_t co
 hipError_t launch_bool_negate(const uint32_t *in, uint32_t *out, size_t total, hipStream_t s);
 hipError_t launch_torus32_from_fraction(const double *fr, uint32_t *acc, uint32_t *set, size_t n, hipStream_t s);
 
+// ---- 128-bit torus (the reference's fft128 path: pbs_f128.hip, dd_device.h, fft128_tables.cpp) ----
+// A u128 word is two little-endian uint64_t (low, high), as unsigned __int128 on host and device.
+struct PbsF128Launch {
+    const unsigned __int128 *lwe_in;   // [count][n+1]
+    unsigned __int128 *lwe_out;        // [count][k*N+1], or [count][(k+1)N] when glwe_out
+    const unsigned __int128 *luts;     // [lut_count][(k+1)*N]
+    const uint32_t *lut_indexes;       // [count] or null; entries >= lut_count read LUT lut_count-1
+    uint32_t lut_count;
+    const double *fbsk;                // [n][level][k+1][k+1][4][M]: planes re.hi, re.lo, im.hi, im.lo
+    const double *twist, *tw;          // [4][M] exp(i pi j / N), [4][M/2] exp(-2 pi i t / M)
+    uint32_t *degrees;                 // scratch [count][n+1]: the modulus-switched input words
+    int n;
+    int base_log, level;               // 2 <= base_log <= 31, level <= 4, base_log * level < 128
+    int modulus_log;                   // 65..128 (128 = native)
+    int count;
+    int glwe_out;
+};
+bool pbs_f128_supported(int N, int k);
+// workgroups (= ciphertexts) of the shape's kernel resident at once on the current device
+int pbs_f128_resident_blocks(int N, int k);
+hipError_t launch_pbs_f128(int N, int k, const PbsF128Launch &a, hipStream_t s);
+// standard u128 key polynomials [npoly][N] -> Fourier planes [npoly][4][M]
+hipError_t launch_bsk128_to_fourier(int N, const void *d_bsk, double *d_fbsk, size_t npoly, const double *twist,
+                                    const double *tw, hipStream_t s);
+// out[i] = acc[i] (0 when null) + backward conversion of the fraction (hi[i], lo[i])
+hipError_t launch_torus128_from_f128(const double *hi, const double *lo, const void *acc, void *out, size_t n,
+                                     hipStream_t s);
+// Canonical host tables (fft128_tables.cpp): every entry hi = RN(x), lo = RN(x - hi) of the exact real x,
+// computed in 256-bit fixed point.  twist: 4 planes of N/2 (cos, sin of pi j / N as re.hi, re.lo, im.hi,
+// im.lo); twiddles: 4 planes of N/4 (exp(-2 pi i t / (N/2))).
+void fft128_host_tables(int N, double *twist, double *twiddles);
+
 // seeded-key decompression (csprng.hip): AES-CTR mask stream of the compression seed written as
 // `row_words` mask words per row, followed by `body_words` copied from d_bodies, for `rows` rows
 size_t aes_tables_bytes();

@@ -219,6 +219,21 @@ SIGNATURES = [
     ("tfhe_mi355_debug_keyswitch_u32", ctypes.c_int,
      [vp, u32p, sz, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, u32p, u32p, sz]),
     ("tfhe_mi355_debug_pbs_u32_resident", ctypes.c_int, [vp, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_context_create_u128", ctypes.c_int,
+     [ctypes.POINTER(TfheMi355Parameters), ctypes.c_int, ctypes.POINTER(vp)]),
+    ("tfhe_mi355_bootstrap_key_upload_u128", ctypes.c_int, [vp, u64p, sz]),
+    ("tfhe_mi355_programmable_bootstrap_u128", ctypes.c_int, [vp, u64p, u64p, u64p, sz, u32p, sz, ctypes.c_uint32]),
+    ("tfhe_mi355_programmable_bootstrap_u128_async", ctypes.c_int,
+     [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp]),
+    ("tfhe_mi355_programmable_bootstrap_u128_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_blind_rotate_u128", ctypes.c_int, [vp, u64p, u64p, u64p, sz, u32p, sz, ctypes.c_uint32]),
+    ("tfhe_mi355_blind_rotate_u128_async", ctypes.c_int, [vp, vp, vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp]),
+    ("tfhe_mi355_blind_rotate_u128_scratch", ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_debug_fft128_tables", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    ("tfhe_mi355_debug_torus128_from_f128", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), u64p, u64p, sz]),
+    ("tfhe_mi355_debug_pbs_u128_resident", ctypes.c_int, [vp, ctypes.POINTER(sz)]),
 ]
 
 _lib = None

@@ -13,6 +13,10 @@
   circuit_bootstrap_boolean                       wop_pbs/mod.rs:243-444
   circuit_bootstrap_boolean_vertical_packing      wop_pbs/mod.rs:647-746
 
+  convert_standard_lwe_bootstrap_key_to_fourier_128
+                                                  lwe_bootstrap_key_conversion.rs:164
+  programmable_bootstrap_f128_lwe_ciphertext      lwe_programmable_bootstrapping.rs:1378-1459
+
 Argument meaning and error behaviour follow the reference: output buffers are caller-owned and
 overwritten; dimension mismatches raise (the reference asserts, lwe_programmable_bootstrapping.rs
 :1088-1102, lwe_keyswitch.rs:106-141).  The `_batch` forms are the engine's native shape.
@@ -92,6 +96,73 @@ def programmable_bootstrap_lwe_ciphertext_batch(inputs: np.ndarray, accumulators
                                                 fourier_bsk: FourierLweBootstrapKey,
                                                 lut_indexes=None) -> np.ndarray:
     return fourier_bsk.engine.programmable_bootstrap(inputs, accumulators, lut_indexes)
+
+
+class Fourier128LweBootstrapKey:
+    """Fourier128LweBootstrapKey (fft128/crypto/bootstrap.rs:24-110) resident on one engine: any object with
+    the u128 methods of Engine (upload_bootstrap_key_u128, programmable_bootstrap_u128, n, big_dim, params)."""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    @property
+    def input_lwe_dimension(self):
+        return self.engine.n
+
+    @property
+    def output_lwe_dimension(self):
+        return self.engine.big_dim
+
+    @property
+    def polynomial_size(self):
+        return self.engine.params.polynomial_size
+
+    @property
+    def glwe_size(self):
+        return self.engine.params.glwe_dimension + 1
+
+
+def convert_standard_lwe_bootstrap_key_to_fourier_128(standard_bsk: np.ndarray, params: ClassicPBSParameters,
+                                                      device: int = 0, engine=None) -> Fourier128LweBootstrapKey:
+    """standard_bsk: uint64 [n, level, k+1, k+1, N, 2] (u128 words as low, high)."""
+    eng = engine or Engine.for_u128(params, device)
+    eng.upload_bootstrap_key_u128(standard_bsk)
+    return Fourier128LweBootstrapKey(eng)
+
+
+def _check_f128(input_shape, output_shape, accumulator_shape, eng) -> None:
+    # lwe_programmable_bootstrapping.rs:1378-1426: the three dimension assertions
+    if len(input_shape) < 2 or input_shape[-1] != 2 or input_shape[-2] != eng.n + 1:
+        raise ValueError(f"Input LWE ciphertext and the bootstrap key's input LweDimension {eng.n} differ "
+                         f"(input shape {tuple(input_shape)}, u128 words as [..., n+1, 2])")
+    if output_shape is not None and (len(output_shape) < 2 or output_shape[-1] != 2
+                                     or output_shape[-2] != eng.big_dim + 1):
+        raise ValueError(f"Output LWE ciphertext and the bootstrap key's output LweDimension {eng.big_dim} differ "
+                         f"(output shape {tuple(output_shape)})")
+    glwe_len = (eng.params.glwe_dimension + 1) * eng.params.polynomial_size
+    if len(accumulator_shape) < 2 or accumulator_shape[-1] != 2 or accumulator_shape[-2] != glwe_len:
+        raise ValueError(f"Accumulator and the bootstrap key's GlweSize / PolynomialSize differ "
+                         f"(accumulator shape {tuple(accumulator_shape)}, expected [..., {glwe_len}, 2])")
+
+
+def programmable_bootstrap_f128_lwe_ciphertext(input_ct: np.ndarray, output_ct: np.ndarray, accumulator: np.ndarray,
+                                               fourier_bsk: Fourier128LweBootstrapKey,
+                                               ciphertext_modulus_log: int = 128) -> None:
+    """input [n+1, 2], output [kN+1, 2] (overwritten), accumulator [(k+1)N, 2]: uint64 (low, high) u128 words.
+    The reference reads the modulus from the ciphertexts; here it is the last argument (128 = native)."""
+    eng = fourier_bsk.engine
+    _check_f128(np.shape(input_ct), np.shape(output_ct), np.shape(accumulator), eng)
+    output_ct[...] = eng.programmable_bootstrap_u128(
+        input_ct, accumulator, ciphertext_modulus_log=ciphertext_modulus_log).reshape(output_ct.shape)
+
+
+def programmable_bootstrap_f128_lwe_ciphertext_batch(inputs: np.ndarray, accumulators: np.ndarray,
+                                                     fourier_bsk: Fourier128LweBootstrapKey, lut_indexes=None,
+                                                     ciphertext_modulus_log: int = 128) -> np.ndarray:
+    eng = fourier_bsk.engine
+    _check_f128(np.shape(inputs), None, np.shape(accumulators), eng)
+    return eng.programmable_bootstrap_u128(inputs, accumulators, lut_indexes,
+                                           ciphertext_modulus_log=ciphertext_modulus_log)
 
 
 def multi_bit_programmable_bootstrap_lwe_ciphertext(input_ct: np.ndarray, output_ct: np.ndarray,

@@ -752,6 +752,82 @@ class Engine:
         _lib.call("tfhe_mi355_debug_pbs_u32_resident", self._h, ctypes.byref(n))
         return n.value
 
+    # -- 128-bit torus (the reference's fft128 path; include/tfhe_mi355.h "128-bit torus") -------------
+    # A u128 word is two uint64 (low, high): host arrays are uint64 of shape [..., words, 2], device
+    # tensors torch.int64 of the same shape.  A context holds keys of one torus width; single-device.
+    @classmethod
+    def for_u128(cls, params, device: int = 0) -> "Engine":
+        """A context validated against the f128 kernel's limits (tfhe_mi355_context_create_u128) instead of
+        the u64 kernels'; it serves the _u128 calls only."""
+        self = cls.__new__(cls)
+        self.params = params
+        self._cp = c_params(params)
+        h = vp()
+        _lib.call("tfhe_mi355_context_create_u128", ctypes.byref(self._cp), device, ctypes.byref(h))
+        self._h = h
+        self.devices = [device]
+        self.device = device
+        return self
+
+    @staticmethod
+    def _u128(a, words: int) -> np.ndarray:
+        a = _u64(a)
+        if a.ndim < 1 or a.shape[-1] != 2:
+            raise ValueError("u128 arrays are uint64 of shape [..., 2] (low, high)")
+        return a.reshape(-1, words, 2)
+
+    def upload_bootstrap_key_u128(self, standard_bsk) -> None:
+        b = _u64(standard_bsk)
+        if b.ndim < 1 or b.shape[-1] != 2:
+            raise ValueError("u128 arrays are uint64 of shape [..., 2] (low, high)")
+        b = b.ravel()
+        _lib.call("tfhe_mi355_bootstrap_key_upload_u128", self._h, _ptr(b), b.size // 2)
+
+    def _call_u128(self, fn: str, lwe_in, luts, lut_indexes, ciphertext_modulus_log: int, out_words: int):
+        x = self._u128(lwe_in, self.n + 1)
+        L = _u64(luts)
+        if L.ndim < 2 or L.shape[-1] != 2 or L.shape[-2] != self.glwe_len:
+            raise ValueError(f"lookup tables are uint64 of shape [..., {self.glwe_len}, 2]")
+        L = L.reshape(-1, self.glwe_len, 2)
+        idx, idxp = self._idx(lut_indexes, x.shape[0], L.shape[0])
+        out = np.empty((x.shape[0], out_words, 2), dtype=np.uint64)
+        _lib.call(fn, self._h, _ptr(x), _ptr(out), _ptr(L), L.shape[0], idxp, x.shape[0],
+                  int(ciphertext_modulus_log))
+        return out
+
+    def programmable_bootstrap_u128(self, lwe_in, luts, lut_indexes=None, ciphertext_modulus_log: int = 128):
+        """[count, n+1, 2] -> [count, kN+1, 2]; luts [lut_count, (k+1)N, 2] general GLWE accumulators."""
+        return self._call_u128("tfhe_mi355_programmable_bootstrap_u128", lwe_in, luts, lut_indexes,
+                               ciphertext_modulus_log, self.big_dim + 1)
+
+    def blind_rotate_u128(self, lwe_in, luts, lut_indexes=None, ciphertext_modulus_log: int = 128):
+        """The blind rotation without the sample extraction: [count, (k+1)N, 2]."""
+        return self._call_u128("tfhe_mi355_blind_rotate_u128", lwe_in, luts, lut_indexes, ciphertext_modulus_log,
+                               self.glwe_len)
+
+    def pbs_u128_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_programmable_bootstrap_u128_scratch", count)
+
+    def blind_rotate_u128_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_blind_rotate_u128_scratch", count)
+
+    def programmable_bootstrap_u128_async(self, d_in, d_out, d_luts, lut_count: int, count: int, d_lut_indexes=None,
+                                          ciphertext_modulus_log: int = 128, stream=None, d_scratch=None,
+                                          glwe_out: bool = False) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.pbs_u128_scratch_bytes(count), stream)
+        fn = "tfhe_mi355_blind_rotate_u128_async" if glwe_out else "tfhe_mi355_programmable_bootstrap_u128_async"
+        _lib.call(fn, self._h, _dev_ptr(d_in), _dev_ptr(d_out), _dev_ptr(d_luts), lut_count,
+                  _dev_ptr(d_lut_indexes), count, int(ciphertext_modulus_log), sp, sb, _stream_ptr(stream))
+
+    def blind_rotate_u128_async(self, d_in, d_out, d_luts, lut_count: int, count: int, **kw) -> None:
+        self.programmable_bootstrap_u128_async(d_in, d_out, d_luts, lut_count, count, glwe_out=True, **kw)
+
+    def pbs_u128_resident(self) -> int:
+        """Ciphertexts (= workgroups) of the f128 PBS kernel resident at once on the device."""
+        n = sz()
+        _lib.call("tfhe_mi355_debug_pbs_u128_resident", self._h, ctypes.byref(n))
+        return n.value
+
     def _scratch_query(self, fn: str, count: int) -> int:
         b = ctypes.c_size_t()
         _lib.call(fn, self._h, count, ctypes.byref(b))
@@ -883,6 +959,28 @@ def debug_torus32_from_fraction(fr, acc=None, device: int = 0):
     _lib.call("tfhe_mi355_debug_torus32_from_fraction", device, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
               _ptr32(a), _ptr32(x), f.size)
     return a, x
+
+
+def debug_fft128_tables(N: int):
+    """(twist [4, N/2], twiddles [4, N/4]): the engine's canonical double-double tables (host only)."""
+    f64p = ctypes.POINTER(ctypes.c_double)
+    tw, w = np.empty((4, N // 2), dtype=np.float64), np.empty((4, N // 4), dtype=np.float64)
+    _lib.call("tfhe_mi355_debug_fft128_tables", N, tw.ctypes.data_as(f64p), w.ctypes.data_as(f64p))
+    return tw, w
+
+
+def debug_torus128_from_f128(hi, lo, acc=None, device: int = 0) -> np.ndarray:
+    """acc + X ([count, 2] uint64), X the f128 kernel's backward conversion of the double-double hi + lo."""
+    f64p = ctypes.POINTER(ctypes.c_double)
+    h = np.ascontiguousarray(hi, dtype=np.float64).ravel()
+    l = np.ascontiguousarray(lo, dtype=np.float64).ravel()
+    if h.size != l.size:
+        raise ValueError("hi and lo must have the same size")
+    a = None if acc is None else _u64(acc).reshape(h.size, 2)
+    out = np.empty((h.size, 2), dtype=np.uint64)
+    _lib.call("tfhe_mi355_debug_torus128_from_f128", device, h.ctypes.data_as(f64p), l.ctypes.data_as(f64p),
+              None if a is None else _ptr(a), _ptr(out), h.size)
+    return out
 
 
 def fill_accumulator(params: ClassicPBSParameters, f) -> np.ndarray:

@@ -147,6 +147,17 @@ GADGET_ALL = [GADGET_DEFAULT_PARAMETERS, GADGET_SIMON_PARAMETERS_40, GADGET_ZAMA
 
 TEST_PARAMS_4_BITS_NATIVE_U64 = PARAM_MESSAGE_2_CARRY_2_KS_PBS.with_(name="TEST_PARAMS_4_BITS_NATIVE_U64")
 
+# The two sets of the reference's f128 PBS test (algorithms/test/lwe_programmable_bootstrapping.rs:169-205):
+# u128 words, message_modulus = 2^message_modulus_log with one bit of padding; the second set computes
+# modulo 2^127 (Engine.programmable_bootstrap_u128(..., ciphertext_modulus_log=127)).
+TEST_PARAMS_4_BITS_NATIVE_U128 = ClassicPBSParameters(
+    lwe_dimension=742, glwe_dimension=1, polynomial_size=2048, lwe_modular_std_dev=4.9982771e-11,
+    glwe_modular_std_dev=8.6457178e-32, pbs_base_log=23, pbs_level=1, ks_base_log=3, ks_level=5,
+    message_modulus=16, carry_modulus=1, name="TEST_PARAMS_4_BITS_NATIVE_U128")
+TEST_PARAMS_3_BITS_127_U128 = TEST_PARAMS_4_BITS_NATIVE_U128.with_(message_modulus=8,
+                                                                   name="TEST_PARAMS_3_BITS_127_U128")
+U128_CIPHERTEXT_MODULUS_LOG = {"TEST_PARAMS_4_BITS_NATIVE_U128": 128, "TEST_PARAMS_3_BITS_127_U128": 127}
+
 # Every shortint ClassicPBSParameters set of the reference (shortint/parameters/mod.rs:598-1201):
 # (name, source line, n, k, N, lwe std, glwe std, pbs base_log, pbs level, ks base_log, ks level,
 #  message modulus, carry modulus, encryption key choice)
