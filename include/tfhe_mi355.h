@@ -59,6 +59,14 @@
  *     d_scratch = NULL), so concurrent callers on different streams only need scratch buffers
  *     of their own, and the calls can be captured into a hipGraph (no allocation or
  *     synchronisation inside);
+ *   - every device pointer handed to an _async entry point (inputs, outputs, LUTs, index and opcode
+ *     arrays, Fourier GGSW lists, key sources, d_scratch) must be 16-byte aligned at its base; rows
+ *     inside a buffer follow from the row lengths (8-byte alignment for u64 rows, 4 for u32 rows, 16
+ *     for u128 rows).  Nothing needs more: the calls are tested with every base at 16 modulo 256.
+ *     An _async call writes nothing outside rows [0, count) of its output (for the strided calls:
+ *     the words the call names) and bytes [0, scratch_bytes) of d_scratch -- not its inputs, not a
+ *     byte next to either -- and its result does not depend on what the output or the scratch held
+ *     before the call (in-place operands excepted: they are inputs);
  *   - keys: a key upload (any *_key_upload*, *_set_ready) waits for the coalesced batches in
  *     flight and blocks new ones until it is done (a pending upload also keeps new batches from
  *     starting, so uploads are not starved under load); the serialized-key uploads hold the key

@@ -712,6 +712,15 @@ class Engine:
         _lib.call(fn, self._h, _dev_ptr(d_in), _dev_ptr(d_out), _dev_ptr(d_luts), lut_count,
                   _dev_ptr(d_lut_indexes), count, sp, sb, _stream_ptr(stream))
 
+    def blind_rotate_u32_scratch_bytes(self, count: int) -> int:
+        return self._scratch_query("tfhe_mi355_blind_rotate_u32_scratch", count)
+
+    def blind_rotate_u32_async(self, d_in, d_glwe_out, d_luts, lut_count: int, count: int, d_lut_indexes=None,
+                               stream=None, d_scratch=None) -> None:
+        sp, sb, _keep = self._scratch(d_scratch, self.blind_rotate_u32_scratch_bytes(count), stream)
+        _lib.call("tfhe_mi355_blind_rotate_u32_async", self._h, _dev_ptr(d_in), _dev_ptr(d_glwe_out), _dev_ptr(d_luts),
+                  lut_count, _dev_ptr(d_lut_indexes), count, sp, sb, _stream_ptr(stream))
+
     def keyswitch_u32_async(self, d_in, d_out, count: int, stream=None, d_scratch=None) -> None:
         sp, sb, _keep = self._scratch(d_scratch, self.ks_u32_scratch_bytes(count), stream)
         _lib.call("tfhe_mi355_keyswitch_u32_async", self._h, _dev_ptr(d_in), _dev_ptr(d_out), count, sp, sb,
