@@ -2,40 +2,12 @@
 // context = device + parameter set + key material + FFT tables, guarded by a mutex so that
 // concurrent callers (the reference's rayon workers, shortint/engine/mod.rs:23-25) can share one
 // key.  Error convention: 0/1 return + thread-local message (tfhe/src/c_api/utils.rs:3-73).
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>  // types only: librccl is opened at run time, when keys are replicated
+// This file: contexts, key transactions and uploads, the kernel-form policy with its scratch sizes, the u64
+// PBS and keyswitch launchers and entry points; the other subsystems are the capi_*.cpp files (capi_internal.h).
+#include "capi_internal.h"
 
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <condition_variable>
-#include <cstdlib>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <deque>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <atomic>
-#include <shared_mutex>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "../../include/tfhe_mi355.h"
-#include "engine.h"
-#include "errors.h"
-
-using namespace tfhe_mi355;
-
-namespace {
-
-struct Failure : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
+namespace tfhe_mi355 {
+namespace capi {
 
 [[noreturn]] void fail(const char *fmt, ...) {
     char buf[512];
@@ -50,345 +22,42 @@ void check(hipError_t e, const char *what) {
     if (e != hipSuccess) fail("%s: %s", what, hipGetErrorString(e));
 }
 
-// The calling thread's current HIP device is the caller's (a Rust or C caller may use HIP itself):
-// every entry point that selects another device puts the caller's back before it returns, success
-// or failure.  A thread without a device (no GPU, or HIP not initialised) keeps none.
-struct CallerDevice {
-    int d = -1;
-    CallerDevice() {
-        if (hipGetDevice(&d) != hipSuccess) d = -1;
-    }
-    ~CallerDevice() {
-        int now = -1;
-        if (d >= 0 && (hipGetDevice(&now) != hipSuccess || now != d)) (void)hipSetDevice(d);
-    }
-    CallerDevice(const CallerDevice &) = delete;
-    CallerDevice &operator=(const CallerDevice &) = delete;
-};
-
-template <class F>
-int guarded(F &&f) {
-    CallerDevice keep;
-    try {
-        f();
-        last_error_text().clear();
-        return TFHE_MI355_OK;
-    } catch (const std::exception &ex) {
-        last_error_text() = ex.what();
-        return TFHE_MI355_ERROR;
-    } catch (...) {
-        last_error_text() = "unknown failure";
-        return TFHE_MI355_ERROR;
-    }
-}
-
-struct DeviceBuffer {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
-    ~DeviceBuffer() { release(); }
-    void reserve(size_t b) {
-        if (b <= bytes) return;
-        if (ptr) check(hipFree(ptr), "hipFree");
-        ptr = nullptr;
-        bytes = 0;
-        check(hipMalloc(&ptr, b), "hipMalloc");
-        bytes = b;
-    }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-};
-
-// page-locked host staging of the host-pointer entry points (hipHostMalloc), one per pipeline lane
-struct PinnedBuffer {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    PinnedBuffer() = default;
-    PinnedBuffer(const PinnedBuffer &) = delete;
-    PinnedBuffer &operator=(const PinnedBuffer &) = delete;
-    ~PinnedBuffer() { release(); }
-    void reserve(size_t b) {
-        if (b <= bytes) return;
-        release();
-        check(hipHostMalloc(&ptr, b, hipHostMallocDefault), "hipHostMalloc");
-        bytes = b;
-    }
-    void release() {
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-};
-
-// an environment switch is on when set to a non-empty value other than "0"
 bool env_flag(const char *name) {
     const char *e = std::getenv(name);
     return e && *e && std::strcmp(e, "0") != 0;
 }
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-bool is_pow2(uint32_t x) { return x && !(x & (x - 1)); }
-}  // namespace
-
-// one small host-pointer call waiting to be coalesced into a batch (see "request coalescing")
-enum CoalescedOp { CO_PBS = 0, CO_KS_PBS, CO_PBS_KS, CO_KS, CO_OPS };
-struct CoalescedReq {
-    const uint64_t *in;
-    uint64_t *out;
-    const uint64_t *luts;
-    size_t lut_count;
-    const uint32_t *idx;
-    size_t count;
-    bool sync = false;  // a blocking caller (coalesced_call), not a submitted request
-    // blocking callers copy their own rows out of the slot's pinned staging once woken (in parallel
-    // instead of one after the other on the dispatcher), then release the slot (pending)
-    const uint64_t *src = nullptr;
-    size_t src_bytes = 0;
-    std::atomic<int> *pending = nullptr;
-    // completion: set by the dispatcher, waited on by the caller alone (no shared mutex, so a
-    // finished batch wakes its callers without a thundering herd on the queue lock)
-    std::mutex m;
-    std::condition_variable cv;
-    bool done = false;
-    std::string err;
-};
-
-struct RcclComms;  // communicator over a multi-device context's distinct devices (key replication)
-
-// Worker threads of a multi-device context, one per shard after the first, started with the context
-// and joined by its destroy: a batched host-pointer call hands each of them its shard's row share
-// (split_rows) instead of starting threads per call.  Each worker runs its queue in
-// order; concurrent calls queue behind each other per shard, as they would on the shard's lock.
-struct ShardWorker {
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<std::function<void()>> q;
-    bool stop = false;
-    std::thread t;
-    void post(std::function<void()> f) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            q.push_back(std::move(f));
-        }
-        cv.notify_one();
-    }
-    void loop() {
-        for (;;) {
-            std::function<void()> f;
-            {
-                std::unique_lock<std::mutex> g(m);
-                cv.wait(g, [&] { return stop || !q.empty(); });
-                if (q.empty()) return;  // stop with nothing queued
-                f = std::move(q.front());
-                q.pop_front();
-            }
-            f();
-        }
-    }
-    ~ShardWorker() {
-        {
-            std::lock_guard<std::mutex> g(m);
-            stop = true;
-        }
-        cv.notify_one();
-        if (t.joinable()) t.join();
-    }
-};
-
-struct TfheMi355Context {
-    TfheMi355Parameters p{};
-    int device = 0;
-    int cus = 256;  // compute units of the device (the latency kernels run one ciphertext per CU)
-    std::mutex mu;
-    // Key material vs the coalescer's batches: every key upload holds it exclusively, every
-    // dispatcher batch shared, so a re-upload waits for the batches in flight and no batch starts
-    // on a half-written key (the large host-pointer calls are ordered with uploads by `mu`).
-    // Uploads go through KeyWrite, batches through KeyRead.
-    std::shared_mutex keys_mu;
-    // key writers waiting or running: a batch does not take keys_mu while one is pending, so an
-    // upload is never starved by back-to-back batches (libstdc++'s shared_mutex lets new readers
-    // in ahead of a waiting writer)
-    std::atomic<int> key_writers{0};
-    // Multi-device context (tfhe_mi355_context_create_devices): one single-device context per
-    // listed device (a device may repeat), owned by this one; empty for a single-device context.
-    // Every entry point of a multi-device context dispatches to them (see "multi-device").
-    std::vector<TfheMi355Context *> shards;
-    std::atomic<size_t> next_shard{0};  // round robin of coalesced calls and submits
-    std::vector<std::unique_ptr<ShardWorker>> workers;  // shards 1.. (split_rows)
-    int replication = 0;  // how the last key replication ran (tfhe_mi355_context_replication)
-    RcclComms *rccl = nullptr;
-    std::string replicate_note;  // why the last replication did not use RCCL in auto mode (empty: it did, or no need)
-    TfheMi355Context *owner = nullptr;  // a shard: its multi-device context (destroyed with it)
-    bool multi() const { return !shards.empty(); }
-    hipStream_t stream = nullptr;
-    FftTables tables;
-    DeviceBuffer fbsk, ksk, std_staging;
-    DeviceBuffer io_luts, io_tmp;
-    DeviceBuffer ksk_planes;   // int8 byte planes of the KSK for the MFMA keyswitch
-    // Host-pointer entry points: kernels run in chunk order on `stream`; each of two lanes has a
-    // copy stream, page-locked staging and device in/out buffers, so that chunk i's copies (and
-    // the host-side copies into and out of the staging) overlap chunk i+-1's kernels.  Only the
-    // synchronous entry points use these, under `mu`; the _async entry points take all their
-    // scratch from the caller (no shared mutable state, capturable into a hipGraph).
-    struct Lane {
-        hipStream_t stream = nullptr;
-        hipEvent_t h2d = nullptr, kern = nullptr, done = nullptr;
-        PinnedBuffer h_in, h_out, h_idx;
-        DeviceBuffer d_in, d_out, d_idx;
-        bool pending = false;
-        bool direct_out = false;  // this chunk's D2H went straight into the caller's pinned buffer
-        size_t first = 0, count = 0;
-    } lanes[2];
-    bool ksk_planes_ready = false;
-    bool fbsk_ready = false, ksk_ready = false;
-    // LWE -> GLWE packing keyswitching key of the gadget layer (big LWE key -> GLWE key)
-    DeviceBuffer pksk, pksk_planes;
-    uint32_t pks_base_log = 0, pks_level = 0;
-    bool pksk_ready = false, pksk_planes_ready = false;
-    // private functional packing keyswitching keys of the circuit bootstrap (big LWE key -> GLWE key,
-    // one key per GGSW row), in the reference's order; byte planes for the int8-MFMA form
-    DeviceBuffer pfpksk, pfpksk_planes;
-    uint32_t pfks_base_log = 0, pfks_level = 0;
-    bool pfpksk_ready = false, pfpksk_planes_ready = false;
-    // GLWE relinearisation key of the gadget layer's lwe_mult (glwe_mult.hip), the reference's order
-    DeviceBuffer rlk;
-    uint32_t rlk_base_log = 0, rlk_level = 0;
-    bool rlk_ready = false;
-    // 32-bit torus keys (the boolean module's; "32-bit torus" section below).  The Fourier key of a u32
-    // bootstrapping key lives in `fbsk` (same format); a context holds keys of one width only.
-    DeviceBuffer ksk32, ksk32_planes;  // u32 keyswitching key and its four int8 byte planes
-    DeviceBuffer lut_true32;           // the gates' accumulator: trivial GLWE, body all 1 << 29
-    bool fbsk32_ready = false, ksk32_ready = false, ksk32_planes_ready = false;
-    bool has_u32_keys() const { return fbsk32_ready || ksk32_ready; }
-    // 128-bit torus ("128-bit torus" section below): the Fourier key as four f64 planes per polynomial and
-    // the double-double tables of the context's N.  for_u128: created by tfhe_mi355_context_create_u128, whose
-    // shape the u64 and u32 kernels need not take -- such a context serves u128 calls only.
-    DeviceBuffer fbsk128, tables128;
-    bool fbsk128_ready = false, for_u128 = false;
-    bool has_u128_keys() const { return fbsk128_ready; }
-    bool has_u64_keys() const { return fbsk_ready || ksk_ready || pksk_ready || pfpksk_ready || rlk_ready; }
-    KernelTimer timer;  // per-kernel durations (tfhe_mi355_kernel_timing_*), off by default
-    // one u32 the quad CMUX sets when a flag wait timed out (check_quad_fail); allocated zeroed at
-    // creation for the contexts that can take the quad path (quad_max > 0)
-    DeviceBuffer quad_fail;
-    // Request coalescing of small host-pointer calls (the reference calls the PBS one ciphertext
-    // at a time from rayon workers: shortint/server_key/mod.rs:783-857, radix_parallel/mul.rs:
-    // 347-407).  Concurrent calls are queued per op; dispatcher threads (one per batch slot,
-    // started with the first coalesced call) each gather a queue into a batch (after a short
-    // window or when the batch is full) and run it on their slot's stream, staging and scratch;
-    // every caller gets its rows back bit-identical to a call of its own.
-    struct Coalescer {
-        std::mutex m;
-        std::condition_variable cv;  // dispatchers: work queued / stop
-        std::vector<CoalescedReq *> queue[CO_OPS];
-        size_t queued[CO_OPS] = {};
-        size_t queued_sync[CO_OPS] = {};  // of queued[]: rows from blocking callers
-        size_t last_sync_rows[CO_OPS] = {};  // rows of the op's previous batch if all were blocking calls
-        std::chrono::steady_clock::time_point last_arrival[CO_OPS];
-        bool stop = false;
-        std::vector<std::thread> workers;
-        struct Slot {
-            hipStream_t stream = nullptr;
-            PinnedBuffer h_in, h_out;            // h_in / d_in: [LUT sets | input rows | LUT indexes]
-            DeviceBuffer d_in, d_out, d_scratch;
-            std::atomic<int> copies{0};          // callers of the last batch still copying out of h_out
-        } slots[9];  // 0-7: dispatchers; 8: direct calls (coalesced_call)
-        bool direct_busy = false;  // slot 8 in use, under m
-        // statistics (tfhe_mi355_coalesce_stats), under m
-        uint64_t batches = 0, rows = 0, in_flight = 0, max_in_flight = 0;
-        double batch_seconds = 0;
-    } co;
-    KernelTimer *timer_or_null() { return timer.every > 0 ? &timer : nullptr; }
-
-    size_t n() const { return p.lwe_dimension; }
-    size_t k() const { return p.glwe_dimension; }
-    size_t N() const { return p.polynomial_size; }
-    size_t big_dim() const { return k() * N(); }
-    size_t glwe_len() const { return (k() + 1) * N(); }
-    // GGSWs in the key: n (classic) or (n/g) 2^g (multi-bit, lwe_multi_bit_bootstrap_key.rs:40-55)
-    size_t ggsw_count() const {
-        return p.grouping_factor ? (n() / p.grouping_factor) << p.grouping_factor : n();
-    }
-    size_t std_bsk_len() const {
-        return ggsw_count() * p.pbs_level * (k() + 1) * (k() + 1) * N();
-    }
-    size_t fourier_bsk_bytes() const {
-        return ggsw_count() * p.pbs_level * (k() + 1) * (k() + 1) * (N() / 2) * sizeof(double2);
-    }
-    size_t ksk_len() const { return big_dim() * p.ks_level * (n() + 1); }
-    size_t pksk_len(uint32_t level) const { return big_dim() * level * glwe_len(); }
-    size_t pfpksk_len(uint32_t level) const { return (k() + 1) * (big_dim() + 1) * level * glwe_len(); }
-    size_t rlk_len(uint32_t level) const { return k() * (k() + 1) / 2 * level * glwe_len(); }
-};
-
-// A keyswitching key of its own dimensions and decomposition (tfhe_mi355_lwe_keyswitch_key_create): one
-// copy per distinct device of its context, read-only after creation.
-struct TfheMi355KeyswitchKey {
-    TfheMi355Context *ctx = nullptr;
-    size_t in_dim = 0, out_dim = 0;
-    uint32_t base_log = 0, level = 0;
-    bool mfma = false;  // int8 byte planes built: the MFMA form runs
-    struct Part {
-        int device = 0;
-        DeviceBuffer ksk, planes;
-    };
-    std::vector<std::unique_ptr<Part>> parts;
-    const Part *on(int device) const {
-        for (auto &p : parts)
-            if (p->device == device) return p.get();
-        return nullptr;
-    }
-};
+}  // namespace capi
+}  // namespace tfhe_mi355
 
 namespace {
-
-// ---- key transactions ------------------------------------------------------------------------
-// A key write holds the context's mutex and keys_mu exclusively.  It is re-entrant per thread: a
-// transaction (tfhe_mi355::begin_key_transaction, e.g. the serialized-key upload, which uploads the
-// KSK, fills the Fourier buffer and marks it ready through three ABI calls) keeps both locks for its
-// whole duration, and the nested calls on the same context from the same thread skip the locking.
+// the contexts under a key write of this thread (KeyWrite, KeyRead): one list for the whole library
 thread_local std::vector<const TfheMi355Context *> tl_key_writes;
+}  // namespace
 
-struct KeyWrite {
-    TfheMi355Context *c = nullptr;
-    std::unique_lock<std::mutex> g;
-    std::unique_lock<std::shared_mutex> k;
-    explicit KeyWrite(TfheMi355Context *c_) {
-        if (std::find(tl_key_writes.begin(), tl_key_writes.end(), c_) != tl_key_writes.end()) return;
-        c = c_;
-        c->key_writers.fetch_add(1, std::memory_order_acq_rel);
-        g = std::unique_lock<std::mutex>(c->mu);
-        k = std::unique_lock<std::shared_mutex>(c->keys_mu);
-        tl_key_writes.push_back(c);
-    }
-    KeyWrite(const KeyWrite &) = delete;
-    KeyWrite &operator=(const KeyWrite &) = delete;
-    ~KeyWrite() {
-        if (!c) return;
-        tl_key_writes.erase(std::find(tl_key_writes.begin(), tl_key_writes.end(), c));
-        k.unlock();
-        g.unlock();
-        c->key_writers.fetch_sub(1, std::memory_order_acq_rel);
-    }
-};
+KeyWrite::KeyWrite(TfheMi355Context *c_) {
+    if (std::find(tl_key_writes.begin(), tl_key_writes.end(), c_) != tl_key_writes.end()) return;
+    c = c_;
+    c->key_writers.fetch_add(1, std::memory_order_acq_rel);
+    g = std::unique_lock<std::mutex>(c->mu);
+    k = std::unique_lock<std::shared_mutex>(c->keys_mu);
+    tl_key_writes.push_back(c);
+}
+KeyWrite::~KeyWrite() {
+    if (!c) return;
+    tl_key_writes.erase(std::find(tl_key_writes.begin(), tl_key_writes.end(), c));
+    k.unlock();
+    g.unlock();
+    c->key_writers.fetch_sub(1, std::memory_order_acq_rel);
+}
+KeyRead::KeyRead(TfheMi355Context *c) {
+    if (std::find(tl_key_writes.begin(), tl_key_writes.end(), c) != tl_key_writes.end()) return;
+    while (c->key_writers.load(std::memory_order_acquire) > 0)
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    k = std::shared_lock<std::shared_mutex>(c->keys_mu);
+}
 
-// a coalesced batch reads the keys: it waits while an upload is pending (writer preference), then
-// holds keys_mu shared for the batch
-struct KeyRead {
-    std::shared_lock<std::shared_mutex> k;
-    explicit KeyRead(TfheMi355Context *c) {
-        if (std::find(tl_key_writes.begin(), tl_key_writes.end(), c) != tl_key_writes.end()) return;
-        while (c->key_writers.load(std::memory_order_acquire) > 0)
-            std::this_thread::sleep_for(std::chrono::microseconds(20));
-        k = std::shared_lock<std::shared_mutex>(c->keys_mu);
-    }
-};
+namespace {
 
 // cos and sin called separately through opaque pointers (no compiler fusion into sincos, whose
 // last bits can differ): the same tables as the oracle's fft_init, bit for bit.
@@ -433,6 +102,9 @@ void require_not_width128(const TfheMi355Context *c) {
     if (c->for_u128) fail("the context was created for the 128-bit torus: it serves the _u128 calls only");
     if (c->has_u128_keys()) fail("the context holds 128-bit-torus keys: other widths need a context of their own");
 }
+}  // namespace
+
+namespace tfhe_mi355::capi {
 void require_width64(const TfheMi355Context *c) {
     if (c->has_u32_keys()) fail("the context holds 32-bit-torus keys: 64-bit calls need a context of their own");
     require_not_width128(c);
@@ -449,16 +121,20 @@ void require_ksk(TfheMi355Context *c) {
     require_width64(c);
     if (!c->ksk_ready) fail("keyswitching key not uploaded");
 }
+}  // namespace tfhe_mi355::capi
 
+namespace {
 hipError_t convert_bsk(TfheMi355Context *c, const uint64_t *d_std, size_t npoly, hipStream_t s) {
     if (large_pbs_supported((int)c->N(), (int)c->k(), (int)c->p.pbs_level))
         return launch_large_bsk_to_fourier(d_std, (double2 *)c->fbsk.ptr, npoly, c->tables, s);
     return launch_bsk_to_fourier((int)c->N(), d_std, (double2 *)c->fbsk.ptr, npoly, c->tables, s);
 }
+}  // namespace
 
 // ---- scratch sizes -----------------------------------------------------------------------------
 // Every launcher takes its device scratch explicitly: the _async entry points pass the caller's
 // d_scratch (sized by the *_scratch queries), the host-pointer entry points a lane's own buffer.
+namespace tfhe_mi355::capi {
 
 // the split CMUX of N >= 4096 (classic, or multi-bit at the N = 8192 sets): accumulators in scratch
 bool is_large(const TfheMi355Context *c) {
@@ -496,7 +172,9 @@ size_t pbs_scratch_bytes(const TfheMi355Context *c, size_t count) {
     const size_t per_ct = large_pbs_scratch_per_ct((int)c->N(), (int)c->k(), (int)c->p.pbs_level);
     return per_ct * std::min(count, large_chunk(c));
 }
+}  // namespace tfhe_mi355::capi
 
+namespace {
 // The on-chip CMUX (the whole blind rotation in one workgroup: one ciphertext per CU at N = 8192,
 // two per CU at N = 4096) against the split CMUX (a ciphertext's sub-blocks over several CUs, in several
 // launches per CMUX): at 3_3 the split path takes 16.3 / 18.8 / 23.2 / 25.4 ms for 1 / 64 / 96 / 128
@@ -551,8 +229,23 @@ size_t latency_max(const TfheMi355Context *c) {
 }
 
 bool ks_use_mfma(const TfheMi355Context *c) {
+    return !ks_mfma_disabled() && ks_mfma_supported((int)c->big_dim(), (int)c->p.ks_level, (int)c->p.ks_base_log);
+}
+
+// KS -> PBS and PBS -> KS: the intermediate LWE rows (of `words`; the small ones for KS -> PBS, the big ones
+// for PBS -> KS), then (reused in stream order) the KS digits or the PBS chunk scratch
+TailLayout fused_layout(const TfheMi355Context *c, size_t words, size_t count) {
+    TailLayout l;
+    l.rest = align256(count * words * 8);  // the intermediate is at 0
+    l.rest_bytes = std::max(ks_scratch_bytes(c, count), pbs_scratch_bytes(c, count));
+    return l;
+}
+}  // namespace
+
+namespace tfhe_mi355::capi {
+bool ks_mfma_disabled() {
     static const bool disabled = env_flag("TFHE_MI355_KS_NO_MFMA");
-    return !disabled && ks_mfma_supported((int)c->big_dim(), (int)c->p.ks_level, (int)c->p.ks_base_log);
+    return disabled;
 }
 
 size_t ks_scratch_bytes(const TfheMi355Context *c, size_t count) {
@@ -560,27 +253,11 @@ size_t ks_scratch_bytes(const TfheMi355Context *c, size_t count) {
     return count ? ks_mfma_scratch_bytes((int)c->big_dim(), (int)c->p.ks_level, (int)count) : 0;
 }
 
-// The packing key's decomposition (base, level) is part of the key, not of the parameter set, so
-// this size is defined from the key's upload on (the scratch query fails before it); it follows
-// from the decomposition and the MFMA eligibility alone, not from the repack having run.
-bool pks_use_mfma(const TfheMi355Context *c) {
-    static const bool disabled = env_flag("TFHE_MI355_KS_NO_MFMA");
-    return !disabled && c->pks_level &&
-           ks_mfma_supported((int)c->big_dim(), (int)c->pks_level, (int)c->pks_base_log);
-}
-size_t pks_scratch_bytes(const TfheMi355Context *c, size_t count) {
-    if (!pks_use_mfma(c) || count == 0) return 0;
-    return ks_mfma_scratch_bytes((int)c->big_dim(), (int)c->pks_level, (int)count);
-}
-
-// KS -> PBS: the small-LWE intermediate, then (reused in stream order) the KS digits or the PBS
-// chunk scratch
 size_t ks_pbs_scratch_bytes(const TfheMi355Context *c, size_t count) {
-    return align256(count * (c->n() + 1) * 8) + std::max(ks_scratch_bytes(c, count), pbs_scratch_bytes(c, count));
+    return fused_layout(c, c->n() + 1, count).total();
 }
-// PBS -> KS: the big-LWE intermediate, then the PBS or KS scratch
 size_t pbs_ks_scratch_bytes(const TfheMi355Context *c, size_t count) {
-    return align256(count * (c->big_dim() + 1) * 8) + std::max(ks_scratch_bytes(c, count), pbs_scratch_bytes(c, count));
+    return fused_layout(c, c->big_dim() + 1, count).total();
 }
 
 void require_scratch(size_t have, size_t need) {
@@ -591,14 +268,14 @@ void require_scratch(size_t have, size_t need) {
 
 void launch_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, const uint64_t *d_luts,
                     size_t lut_count, const uint32_t *d_idx, size_t count, void *scratch, size_t scratch_bytes,
-                    hipStream_t s, bool glwe_out = false) {
+                    hipStream_t s, bool glwe_out) {
     require_fbsk(c);
     if (lut_count == 0) fail("lut_count must be >= 1");
     if (lut_count > 0xffffffffu) fail("lut_count too large");
     if (count > 0x7fffffff) fail("batch too large");
     if (count == 0) return;
-    if (c->p.grouping_factor && !is_large(c)) {
-        MultiBitPbsLaunch a;
+    // the fields that the classic, multi-bit and large launch arguments share
+    auto common = [&](auto &a) {
         a.lwe_in = d_in;
         a.lwe_out = d_out;
         a.luts = d_luts;
@@ -610,6 +287,10 @@ void launch_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, 
         a.n = (int)c->n();
         a.base_log = (int)c->p.pbs_base_log;
         a.count = (int)count;
+    };
+    if (c->p.grouping_factor && !is_large(c)) {
+        MultiBitPbsLaunch a;
+        common(a);
         a.glwe_out = glwe_out;
         if (count <= latency_max(c) && latency_multibit_supported((int)c->N(), (int)c->k(), (int)c->p.pbs_level,
                                                                  (int)c->p.grouping_factor)) {
@@ -629,18 +310,8 @@ void launch_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, 
             fail("N = %zu PBS needs >= %zu bytes of device scratch per chunk ciphertext (%zu given)", c->N(), per_ct,
                  scratch_bytes);
         LargePbsLaunch a{};
-        a.lwe_in = d_in;
-        a.lwe_out = d_out;
-        a.luts = d_luts;
-        a.lut_indexes = d_idx;
-        a.lut_count = (uint32_t)lut_count;
-        a.fbsk = reinterpret_cast<const double2 *>(c->fbsk.ptr);
-        a.W = c->tables.W;
-        a.twist = c->tables.twist;
+        common(a);
         a.wtop = c->tables.wtop;
-        a.n = (int)c->n();
-        a.base_log = (int)c->p.pbs_base_log;
-        a.count = (int)count;
         a.scratch = scratch;
         a.scratch_bytes = std::min(scratch_bytes, per_ct * large_chunk(c));
         a.timer = c->timer_or_null();
@@ -654,17 +325,7 @@ void launch_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, 
         return;
     }
     ClassicPbsLaunch a;
-    a.lwe_in = d_in;
-    a.lwe_out = d_out;
-    a.luts = d_luts;
-    a.lut_indexes = d_idx;
-    a.lut_count = (uint32_t)lut_count;
-    a.fbsk = reinterpret_cast<const double2 *>(c->fbsk.ptr);
-    a.W = c->tables.W;
-    a.twist = c->tables.twist;
-    a.n = (int)c->n();
-    a.base_log = (int)c->p.pbs_base_log;
-    a.count = (int)count;
+    common(a);
     a.glwe_out = glwe_out;
     // small batches: the latency kernel (one ciphertext per CU, all 8 waves on it; same outputs)
     if (count <= latency_max(c) && latency_pbs_supported((int)c->N(), (int)c->k(), (int)c->p.pbs_level)) {
@@ -718,7 +379,9 @@ void launch_ks_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, s
     }
     check(launch_keyswitch(a, s), "launch keyswitch");
 }
+}  // namespace tfhe_mi355::capi
 
+namespace {
 // keyswitch under a key object, on shard (or single-device context) c
 size_t ks_key_scratch_bytes(const TfheMi355KeyswitchKey *key, size_t count) {
     return key->mfma && count ? ks_mfma_scratch_bytes((int)key->in_dim, (int)key->level, (int)count) : 0;
@@ -745,6 +408,19 @@ void launch_ks_key_dev(TfheMi355Context *c, const TfheMi355KeyswitchKey *key, co
         return;
     }
     check(key->base_log > 7 ? launch_keyswitch_wide(a, s) : launch_keyswitch(a, s), "launch keyswitch");
+}
+
+
+// The packing key's decomposition (base, level) is part of the key, not of the parameter set, so
+// this size is defined from the key's upload on (the scratch query fails before it); it follows
+// from the decomposition and the MFMA eligibility alone, not from the repack having run.
+bool pks_use_mfma(const TfheMi355Context *c) {
+    return !ks_mfma_disabled() && c->pks_level &&
+           ks_mfma_supported((int)c->big_dim(), (int)c->pks_level, (int)c->pks_base_log);
+}
+size_t pks_scratch_bytes(const TfheMi355Context *c, size_t count) {
+    if (!pks_use_mfma(c) || count == 0) return 0;
+    return ks_mfma_scratch_bytes((int)c->big_dim(), (int)c->pks_level, (int)count);
 }
 
 // LWE -> GLWE packing keyswitch (lwe_packing_keyswitch.rs:102-186): the LWE keyswitch GEMM with
@@ -777,7 +453,9 @@ void launch_packing_ks_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *
         check(launch_keyswitch(a, s), "launch packing keyswitch");
     }
 }
+}  // namespace
 
+namespace tfhe_mi355::capi {
 // shortint KS -> PBS on device: scratch = [small LWE intermediate | KS digits or PBS chunk scratch]
 void launch_ks_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, const uint64_t *d_luts,
                        size_t lut_count, const uint32_t *d_idx, size_t count, void *scratch, size_t scratch_bytes,
@@ -785,12 +463,12 @@ void launch_ks_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_ou
     require_fbsk(c);
     require_ksk(c);
     if (count == 0) return;
-    require_scratch(scratch ? scratch_bytes : 0, ks_pbs_scratch_bytes(c, count));
-    const size_t head = align256(count * (c->n() + 1) * 8);
-    uint64_t *small = reinterpret_cast<uint64_t *>(scratch);
-    void *rest = reinterpret_cast<char *>(scratch) + head;
-    launch_ks_dev(c, d_in, small, count, rest, scratch_bytes - head, s);
-    launch_pbs_dev(c, small, d_out, d_luts, lut_count, d_idx, count, rest, scratch_bytes - head, s);
+    const TailLayout l = fused_layout(c, c->n() + 1, count);
+    require_scratch(scratch ? scratch_bytes : 0, l.total());
+    uint64_t *small = scratch_at<uint64_t>(scratch, 0);
+    void *rest = scratch_at(scratch, l.rest);
+    launch_ks_dev(c, d_in, small, count, rest, scratch_bytes - l.rest, s);
+    launch_pbs_dev(c, small, d_out, d_luts, lut_count, d_idx, count, rest, scratch_bytes - l.rest, s);
 }
 
 // shortint PBS -> KS on device: scratch = [big LWE intermediate | PBS or KS scratch]
@@ -800,14 +478,16 @@ void launch_pbs_ks_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_ou
     require_fbsk(c);
     require_ksk(c);
     if (count == 0) return;
-    require_scratch(scratch ? scratch_bytes : 0, pbs_ks_scratch_bytes(c, count));
-    const size_t head = align256(count * (c->big_dim() + 1) * 8);
-    uint64_t *big = reinterpret_cast<uint64_t *>(scratch);
-    void *rest = reinterpret_cast<char *>(scratch) + head;
-    launch_pbs_dev(c, d_in, big, d_luts, lut_count, d_idx, count, rest, scratch_bytes - head, s);
-    launch_ks_dev(c, big, d_out, count, rest, scratch_bytes - head, s);
+    const TailLayout l = fused_layout(c, c->big_dim() + 1, count);
+    require_scratch(scratch ? scratch_bytes : 0, l.total());
+    uint64_t *big = scratch_at<uint64_t>(scratch, 0);
+    void *rest = scratch_at(scratch, l.rest);
+    launch_pbs_dev(c, d_in, big, d_luts, lut_count, d_idx, count, rest, scratch_bytes - l.rest, s);
+    launch_ks_dev(c, big, d_out, count, rest, scratch_bytes - l.rest, s);
 }
+}  // namespace tfhe_mi355::capi
 
+namespace {
 void launch_glwe_poly_mul_dev(TfheMi355Context *c, const uint64_t *d_glwe, size_t glwe_per_item,
                               const uint64_t *d_polys, size_t npoly, size_t count, bool extract, uint64_t *d_out,
                               hipStream_t s) {
@@ -884,10 +564,19 @@ void launch_glwe_mult_dev(TfheMi355Context *c, const uint64_t *d_lhs, const uint
 
 // lwe_mult: scratch = [2 count LWE rows, lhs then rhs | their packed GLWEs | packing-KS digits, then
 // (reused in stream order) the product's T/R polynomials]
-size_t lwe_mult_scratch(const TfheMi355Context *c, size_t count) {
-    return align256(2 * count * (c->big_dim() + 1) * 8) + align256(2 * count * c->glwe_len() * 8) +
-           std::max(align256(pks_scratch_bytes(c, 2 * count)), glwe_mult_scratch(c, count));
+struct LweMultLayout : TailLayout {
+    size_t packed;  // the rows are at 0
+};
+LweMultLayout lwe_mult_layout(const TfheMi355Context *c, size_t count) {
+    ScratchCursor at;
+    LweMultLayout l;
+    at.take(2 * count * (c->big_dim() + 1) * 8);
+    l.packed = at.take(2 * count * c->glwe_len() * 8);
+    l.rest = at.off;
+    l.rest_bytes = std::max(align256(pks_scratch_bytes(c, 2 * count)), glwe_mult_scratch(c, count));
+    return l;
 }
+size_t lwe_mult_scratch(const TfheMi355Context *c, size_t count) { return lwe_mult_layout(c, count).total(); }
 
 void launch_lwe_mult_dev(TfheMi355Context *c, const uint64_t *d_lhs, const uint64_t *d_rhs, uint32_t log_p,
                          uint64_t *d_out, size_t count, void *scratch, size_t scratch_bytes, hipStream_t s) {
@@ -900,13 +589,12 @@ void launch_lwe_mult_dev(TfheMi355Context *c, const uint64_t *d_lhs, const uint6
     const size_t lwe = c->big_dim() + 1, glwe = c->glwe_len();
     if (words_overlap(d_out, count * lwe, d_lhs, count * lwe) || words_overlap(d_out, count * lwe, d_rhs, count * lwe))
         fail("lwe_mult: out overlaps an input");
-    require_scratch(scratch ? scratch_bytes : 0, lwe_mult_scratch(c, count));
-    char *p = reinterpret_cast<char *>(scratch);
-    uint64_t *rows = reinterpret_cast<uint64_t *>(p);
-    p += align256(2 * count * lwe * 8);
-    uint64_t *packed = reinterpret_cast<uint64_t *>(p);
-    p += align256(2 * count * glwe * 8);
-    const size_t rest = scratch_bytes - (size_t)(p - reinterpret_cast<char *>(scratch));
+    const LweMultLayout l = lwe_mult_layout(c, count);
+    require_scratch(scratch ? scratch_bytes : 0, l.total());
+    uint64_t *rows = scratch_at<uint64_t>(scratch, 0);
+    uint64_t *packed = scratch_at<uint64_t>(scratch, l.packed);
+    void *p = scratch_at(scratch, l.rest);
+    const size_t rest = scratch_bytes - l.rest;
     check(hipMemcpyAsync(rows, d_lhs, count * lwe * 8, hipMemcpyDeviceToDevice, s), "gather lhs");
     check(hipMemcpyAsync(rows + count * lwe, d_rhs, count * lwe * 8, hipMemcpyDeviceToDevice, s), "gather rhs");
     {
@@ -939,6 +627,9 @@ void host_pair_call(TfheMi355Context *ctx, const uint64_t *lhs, const uint64_t *
     }
 }
 size_t ggsw_polys(const TfheMi355Context *c, uint32_t level) { return (size_t)level * (c->k() + 1) * (c->k() + 1); }
+}  // namespace
+
+namespace tfhe_mi355::capi {
 size_t ggsw_std_words(const TfheMi355Context *c, uint32_t level) { return ggsw_polys(c, level) * c->N(); }
 size_t ggsw_fourier_bytes(const TfheMi355Context *c, uint32_t level) {
     return ggsw_polys(c, level) * (c->N() / 2) * sizeof(double2);
@@ -952,6 +643,15 @@ void require_ggsw_shape(const TfheMi355Context *c, uint32_t base_log, uint32_t l
              base_log, level);
 }
 
+void ggsw_list_to_fourier_dev(TfheMi355Context *c, const uint64_t *d_std, double2 *d_fourier, size_t ggsw_count,
+                              uint32_t level, hipStream_t s) {
+    TimedLaunch tl(c->timer_or_null(), "ggsw_to_fourier", s);
+    check(launch_bsk_to_fourier((int)c->N(), d_std, d_fourier, ggsw_count * ggsw_polys(c, level), c->tables, s),
+          "launch GGSW list conversion");
+}
+}  // namespace tfhe_mi355::capi
+
+namespace {
 void validate_ggsw_indexes(const uint32_t *idx, size_t count, size_t ggsw_count) {
     if (!idx) {
         if (ggsw_count < count) fail("GGSW list has %zu ciphertexts for %zu items (no ggsw_indexes)", ggsw_count, count);
@@ -959,13 +659,6 @@ void validate_ggsw_indexes(const uint32_t *idx, size_t count, size_t ggsw_count)
     }
     for (size_t i = 0; i < count; i++)
         if (idx[i] >= ggsw_count) fail("ggsw_indexes[%zu] = %u out of range (ggsw_count %zu)", i, idx[i], ggsw_count);
-}
-
-void ggsw_list_to_fourier_dev(TfheMi355Context *c, const uint64_t *d_std, double2 *d_fourier, size_t ggsw_count,
-                              uint32_t level, hipStream_t s) {
-    TimedLaunch tl(c->timer_or_null(), "ggsw_to_fourier", s);
-    check(launch_bsk_to_fourier((int)c->N(), d_std, d_fourier, ggsw_count * ggsw_polys(c, level), c->tables, s),
-          "launch GGSW list conversion");
 }
 
 GgswCmuxLaunch ggsw_launch_args(TfheMi355Context *c, const double2 *d_fggsw, size_t ggsw_blocks, const uint32_t *d_idx,
@@ -1002,10 +695,24 @@ void launch_ggsw_node_dev(TfheMi355Context *c, int mode, const double2 *d_fggsw,
     check(launch_ggsw_cmux((int)c->N(), (int)c->k(), a, s), "launch GGSW node");
 }
 
+// two ping-pong GLWE buffers per (item, output): the tree's first level leaves npoly/2 nodes, the next
+// npoly/4; without a tree the first holds the rotation steps' accumulator
+// (the first at 0, the second at `rest`)
+TailLayout vp_layout(const TfheMi355Context *c, size_t npoly, size_t nout, size_t count) {
+    const size_t a = std::max<size_t>(npoly / 2, 1), b = std::max<size_t>(npoly / 4, 1);
+    TailLayout l;
+    l.rest = align256(count * nout * a * c->glwe_len() * 8);
+    l.rest_bytes = align256(count * nout * b * c->glwe_len() * 8);
+    return l;
+}
+
+// TFHE_MI355_VP_STEPWISE=1: one launch per rotation step instead of the chain launch (A/B arm); read at
+// every call, so that one process can run both arms
+bool vp_stepwise() { return env_flag("TFHE_MI355_VP_STEPWISE"); }
+}  // namespace
+
+namespace tfhe_mi355::capi {
 // vertical packing: log2(npoly) tree bits, then nbits - log2(npoly) rotation bits
-struct VpShape {
-    uint32_t nt, nr;
-};
 VpShape vp_shape(const TfheMi355Context *c, uint32_t nbits, size_t npoly) {
     if (npoly == 0 || npoly > 0x40000000u || !is_pow2((uint32_t)npoly))
         fail("vertical packing: the LUT has %zu polynomials, not a power of two", npoly);
@@ -1020,16 +727,9 @@ VpShape vp_shape(const TfheMi355Context *c, uint32_t nbits, size_t npoly) {
     return {nt, nbits - nt};
 }
 
-// two ping-pong GLWE buffers per (item, output): the tree's first level leaves npoly/2 nodes, the next
-// npoly/4; without a tree the first holds the rotation steps' accumulator
 size_t vp_scratch_bytes(const TfheMi355Context *c, size_t npoly, size_t nout, size_t count) {
-    const size_t a = std::max<size_t>(npoly / 2, 1), b = std::max<size_t>(npoly / 4, 1);
-    return align256(count * nout * a * c->glwe_len() * 8) + align256(count * nout * b * c->glwe_len() * 8);
+    return vp_layout(c, npoly, nout, count).total();
 }
-
-// TFHE_MI355_VP_STEPWISE=1: one launch per rotation step instead of the chain launch (A/B arm); read at
-// every call, so that one process can run both arms
-bool vp_stepwise() { return env_flag("TFHE_MI355_VP_STEPWISE"); }
 
 // luts [lut_count][nout][npoly][N], d_lwe_out [count][nout][kN+1]: every launch covers the nout outputs
 // of every item (GgswCmuxLaunch::nout), so a tree level is one launch over count nout (npoly >> (j+1))
@@ -1044,12 +744,10 @@ void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, ui
     if (nout == 0 || nout > 0xffffu) fail("vertical packing: nout %zu out of range", nout);
     if (count == 0) return;
     if (count > 0x7fffffffu / (nout * std::max<size_t>(npoly / 2, 1))) fail("count too large");
-    require_scratch(scratch ? scratch_bytes : 0, vp_scratch_bytes(c, npoly, nout, count));
+    const TailLayout l = vp_layout(c, npoly, nout, count);
+    require_scratch(scratch ? scratch_bytes : 0, l.total());
     const size_t glwe = c->glwe_len();
-    uint64_t *buf[2] = {
-        reinterpret_cast<uint64_t *>(scratch),
-        reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(scratch) +
-                                     align256(count * nout * std::max<size_t>(npoly / 2, 1) * glwe * 8))};
+    uint64_t *buf[2] = {scratch_at<uint64_t>(scratch, 0), scratch_at<uint64_t>(scratch, l.rest)};
     GgswCmuxLaunch a = ggsw_launch_args(c, d_fggsw, count, nullptr, base_log, level);
     a.ggsw_per_item = (int)nbits;
     a.lut_indexes = d_lut_idx;
@@ -1113,6 +811,9 @@ void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, ui
         cur = a.out;
     }
 }
+}  // namespace tfhe_mi355::capi
+
+namespace {
 
 // ---- WoP-PBS, the bootstrapped half: pfpks, bit extraction, circuit bootstrap -----------------------
 // The pfpksk list's decomposition belongs to the key (as the packing key's): the scratch sizes are
@@ -1175,10 +876,24 @@ void validate_extract_bits(uint32_t delta_log, uint32_t nbits) {
     if (delta_log == 0 && nbits > 1)
         fail("extract_bits: delta_log 0 with %u bits (the LUT of the lowest bit would be 2^-1)", nbits);
 }
+struct ExtractBitsLayout : TailLayout {
+    size_t shifted, pbs_out, ks_out, lut;  // the running input is at 0
+};
+ExtractBitsLayout extract_bits_layout(const TfheMi355Context *c, size_t count) {
+    const size_t big = count * (c->big_dim() + 1) * 8, small = count * (c->n() + 1) * 8;
+    ScratchCursor at;
+    ExtractBitsLayout l;
+    at.take(big);
+    l.shifted = at.take(big);
+    l.pbs_out = at.take(big);
+    l.ks_out = at.take(small);
+    l.lut = at.take(c->glwe_len() * 8);
+    l.rest = at.off;
+    l.rest_bytes = std::max<size_t>(std::max(ks_scratch_bytes(c, count), pbs_scratch_bytes(c, count)), 256);
+    return l;
+}
 size_t extract_bits_scratch_bytes(const TfheMi355Context *c, size_t count) {
-    const size_t big = align256(count * (c->big_dim() + 1) * 8), small = align256(count * (c->n() + 1) * 8);
-    return 3 * big + small + align256(c->glwe_len() * 8) +
-           std::max<size_t>(std::max(ks_scratch_bytes(c, count), pbs_scratch_bytes(c, count)), 256);
+    return extract_bits_layout(c, count).total();
 }
 void launch_extract_bits_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t delta_log, uint32_t nbits,
                              uint64_t *d_out, size_t count, void *scratch, size_t scratch_bytes, hipStream_t s) {
@@ -1188,17 +903,16 @@ void launch_extract_bits_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t
     validate_extract_bits(delta_log, nbits);
     if (count == 0) return;
     if (count > 0x7fffffffu / nbits) fail("count too large");
-    require_scratch(scratch ? scratch_bytes : 0, extract_bits_scratch_bytes(c, count));
+    const ExtractBitsLayout l = extract_bits_layout(c, count);
+    require_scratch(scratch ? scratch_bytes : 0, l.total());
     const size_t bw = c->big_dim() + 1, sw = c->n() + 1;
-    const size_t big = align256(count * bw * 8), small = align256(count * sw * 8), lut_b = align256(c->glwe_len() * 8);
-    char *p = reinterpret_cast<char *>(scratch);
-    uint64_t *cur = reinterpret_cast<uint64_t *>(p);
-    uint64_t *shifted = reinterpret_cast<uint64_t *>(p + big);
-    uint64_t *pbs_out = reinterpret_cast<uint64_t *>(p + 2 * big);
-    uint64_t *ks_out = reinterpret_cast<uint64_t *>(p + 3 * big);
-    uint64_t *lut = reinterpret_cast<uint64_t *>(p + 3 * big + small);
-    void *rest = p + 3 * big + small + lut_b;
-    const size_t rest_bytes = scratch_bytes - (3 * big + small + lut_b);
+    uint64_t *cur = scratch_at<uint64_t>(scratch, 0);
+    uint64_t *shifted = scratch_at<uint64_t>(scratch, l.shifted);
+    uint64_t *pbs_out = scratch_at<uint64_t>(scratch, l.pbs_out);
+    uint64_t *ks_out = scratch_at<uint64_t>(scratch, l.ks_out);
+    uint64_t *lut = scratch_at<uint64_t>(scratch, l.lut);
+    void *rest = scratch_at(scratch, l.rest);
+    const size_t rest_bytes = scratch_bytes - l.rest;
     check(hipMemcpyAsync(cur, d_in, count * bw * 8, hipMemcpyDeviceToDevice, s), "extract_bits: copy input");
     for (uint32_t b = 0; b < nbits; b++) {
         {
@@ -1231,11 +945,23 @@ void validate_cbs(const TfheMi355Context *c, uint32_t delta_log, uint32_t base_l
     require_ggsw_shape(c, base_log, level);
     if (delta_log > 63) fail("circuit bootstrap: delta_log %u out of range (at most 63)", delta_log);
 }
-size_t cbs_scratch_bytes(const TfheMi355Context *c, uint32_t level, size_t count) {
+struct CbsLayout : TailLayout {
+    size_t luts, idx, pbs_out;  // the shifted rows are at 0
+};
+CbsLayout cbs_layout(const TfheMi355Context *c, uint32_t level, size_t count) {
     const size_t rows = count * level;
-    return align256(rows * (c->n() + 1) * 8) + align256((size_t)level * c->glwe_len() * 8) + align256(rows * 4) +
-           align256(rows * (c->big_dim() + 1) * 8) +
-           std::max<size_t>(std::max(pbs_scratch_bytes(c, rows), pfpks_scratch_bytes(c, rows)), 256);
+    ScratchCursor at;
+    CbsLayout l;
+    at.take(rows * (c->n() + 1) * 8);
+    l.luts = at.take((size_t)level * c->glwe_len() * 8);
+    l.idx = at.take(rows * 4);
+    l.pbs_out = at.take(rows * (c->big_dim() + 1) * 8);
+    l.rest = at.off;
+    l.rest_bytes = std::max<size_t>(std::max(pbs_scratch_bytes(c, rows), pfpks_scratch_bytes(c, rows)), 256);
+    return l;
+}
+size_t cbs_scratch_bytes(const TfheMi355Context *c, uint32_t level, size_t count) {
+    return cbs_layout(c, level, count).total();
 }
 void launch_cbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t delta_log, uint32_t base_log, uint32_t level,
                     uint64_t *d_ggsw_out, size_t count, void *scratch, size_t scratch_bytes, hipStream_t s) {
@@ -1245,17 +971,15 @@ void launch_cbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t delta_lo
     require_pfpksk(c);
     if (count == 0) return;
     if (count > kPfpksMaxRows / level) fail("count too large");
-    require_scratch(scratch ? scratch_bytes : 0, cbs_scratch_bytes(c, level, count));
+    const CbsLayout l = cbs_layout(c, level, count);
+    require_scratch(scratch ? scratch_bytes : 0, l.total());
     const size_t rows = count * level, sw = c->n() + 1, bw = c->big_dim() + 1;
-    const size_t o1 = align256(rows * sw * 8), o2 = o1 + align256((size_t)level * c->glwe_len() * 8),
-                 o3 = o2 + align256(rows * 4), o4 = o3 + align256(rows * bw * 8);
-    char *p = reinterpret_cast<char *>(scratch);
-    uint64_t *shifted = reinterpret_cast<uint64_t *>(p);
-    uint64_t *luts = reinterpret_cast<uint64_t *>(p + o1);
-    uint32_t *idx = reinterpret_cast<uint32_t *>(p + o2);
-    uint64_t *pbs_out = reinterpret_cast<uint64_t *>(p + o3);
-    void *rest = p + o4;
-    const size_t rest_bytes = scratch_bytes - o4;
+    uint64_t *shifted = scratch_at<uint64_t>(scratch, 0);
+    uint64_t *luts = scratch_at<uint64_t>(scratch, l.luts);
+    uint32_t *idx = scratch_at<uint32_t>(scratch, l.idx);
+    uint64_t *pbs_out = scratch_at<uint64_t>(scratch, l.pbs_out);
+    void *rest = scratch_at(scratch, l.rest);
+    const size_t rest_bytes = scratch_bytes - l.rest;
     {
         TimedLaunch tl(c->timer_or_null(), "wop_glue", s);
         check(launch_wop_shift_rows(shifted, d_in, rows, sw, sw, level, (int)(63 - delta_log), (uint64_t)1 << 62, s),
@@ -1311,12 +1035,20 @@ void launch_cbvp_dev(TfheMi355Context *c, const uint64_t *d_in, uint32_t nbits, 
     launch_vertical_packing_dev(c, ggsw_f, base_log, level, nbits, d_luts, lut_count, nout, npoly, d_lut_idx, count,
                                 d_out, rest, l.rest_b, s);
 }
+}  // namespace
 
+namespace tfhe_mi355::capi {
 void validate_lut_indexes(const uint32_t *idx, size_t count, size_t lut_count) {
     if (!idx) return;
     for (size_t i = 0; i < count; i++)
         if (idx[i] >= lut_count) fail("lut_indexes[%zu] = %u out of range (lut_count %zu)", i, idx[i], lut_count);
 }
+
+// an ABI call made from inside another one: its failure text becomes ours
+void abi(int rc) {
+    if (rc != TFHE_MI355_OK) fail("%s", tfhe_mi355_last_error());
+}
+}  // namespace tfhe_mi355::capi
 
 // ---- host-pointer pipeline ------------------------------------------------------------------------
 // The synchronous entry points (host buffers in and out, the form the Rust binding calls) run the
@@ -1325,11 +1057,7 @@ void validate_lut_indexes(const uint32_t *idx, size_t count, size_t lut_count) {
 // stays busy), and the output is DMA'd back on the copy stream and copied into the caller's
 // buffer while the next chunk's kernels run.  The LUTs go up once per call.  Callers are
 // serialised by ctx->mu.
-
-using ChunkLaunch = void (*)(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, const uint64_t *d_luts,
-                             size_t lut_count, const uint32_t *d_idx, size_t count, void *scratch,
-                             size_t scratch_bytes, hipStream_t s);
-using ScratchSize = size_t (*)(const TfheMi355Context *c, size_t count);
+namespace {
 
 size_t host_chunk(const TfheMi355Context *c, size_t count) {
     static const size_t forced = [] {
@@ -1383,7 +1111,9 @@ void check_quad_fail(TfheMi355Context *c) {
              "kernels on this GPU?); the outputs are invalid -- TFHE_MI355_QUAD=0 disables the quad CMUX");
     }
 }
+}  // namespace
 
+namespace tfhe_mi355::capi {
 void run_host_pipeline(TfheMi355Context *c, const uint64_t *in, size_t in_words, uint64_t *out, size_t out_words,
                        const uint64_t *luts, size_t lut_words, size_t lut_count, const uint32_t *idx, size_t count,
                        ChunkLaunch launch, ScratchSize scratch_size) {
@@ -1467,14 +1197,18 @@ void chunk_pbs(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64
                size_t n, void *sc, size_t sb, hipStream_t s) {
     launch_pbs_dev(c, i, o, l, lc, x, n, sc, sb, s);
 }
-void chunk_blind_rotate(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *l, size_t lc,
-                        const uint32_t *x, size_t n, void *sc, size_t sb, hipStream_t s) {
-    launch_pbs_dev(c, i, o, l, lc, x, n, sc, sb, s, true);
-}
 void chunk_ks(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *, size_t, const uint32_t *,
               size_t n, void *sc, size_t sb, hipStream_t s) {
     launch_ks_dev(c, i, o, n, sc, sb, s);
 }
+}  // namespace tfhe_mi355::capi
+
+namespace {
+void chunk_blind_rotate(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *l, size_t lc,
+                        const uint32_t *x, size_t n, void *sc, size_t sb, hipStream_t s) {
+    launch_pbs_dev(c, i, o, l, lc, x, n, sc, sb, s, true);
+}
+
 void chunk_pks(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *, size_t, const uint32_t *,
                size_t n, void *sc, size_t sb, hipStream_t s) {
     launch_packing_ks_dev(c, i, o, n, sc, sb, s);
@@ -1762,7 +1496,9 @@ bool coalesce_direct() {
     static const bool v = env_size("TFHE_MI355_COALESCE_DIRECT", 1) != 0;
     return v;
 }
+}  // namespace
 
+namespace tfhe_mi355::capi {
 // the calling thread's request joins its op's queue and waits for its own completion
 void coalesced_call(TfheMi355Context *c, CoalescedOp op, CoalescedReq &r) {
     auto &co = c->co;
@@ -1802,273 +1538,6 @@ void coalesced_call(TfheMi355Context *c, CoalescedOp op, CoalescedReq &r) {
 }
 
 bool coalescible(size_t count) { return count > 0 && count <= coalesce_max_count(); }
-
-// an ABI call made from inside another one: its failure text becomes ours
-void abi(int rc) {
-    if (rc != TFHE_MI355_OK) fail("%s", tfhe_mi355_last_error());
-}
-
-// ---- multi-device contexts ----------------------------------------------------------------------
-// SURVEY.md 8b `ctx_create(params, device_mask)` / 8e: ONE process drives several GPUs through one
-// context, the way the reference's one process drives its rayon pool (a thread-local ShortintEngine
-// per worker, shortint/engine/mod.rs:23-25, and one KS+PBS per block from par_iter,
-// integer/server_key/radix_parallel/mul.rs:347-407, through the ShortintBootstrappingKey arms,
-// shortint/server_key/mod.rs:104-111,783-857).  A multi-device context owns one single-device context
-// ("shard") per listed device; a device may be listed more than once (shards on one GPU then run
-// side by side on their own streams).
-//   keys: uploaded once, to the first shard, and replicated from its device memory: an RCCL
-//     broadcast over xGMI among the distinct devices (librccl opened at run time; ncclCommInitAll
-//     over the device list, one rank per distinct device), then device-to-device copies to further
-//     shards on the same device.  TFHE_MI355_REPLICATE=copy uses peer copies instead of RCCL,
-//     =rccl forces the broadcast even with one distinct device (a one-rank communicator copying
-//     into the second shard of that device; a test hook);
-//   batched host-pointer calls: split into contiguous shares, one per shard, each run by the shard's
-//     own entry point on a thread of its own (its own stream, staging, lock) and joined before the
-//     call returns;
-//   small calls (the coalesced ones) and submitted requests: round-robin to the shards' coalescers;
-//   device-pointer (_async) calls and their scratch queries: the first device's shard (a device
-//     pointer belongs to one device; tfhe_mi355_context_device_context hands out each shard).
-}  // namespace
-
-struct RcclComms {
-    void *lib = nullptr;
-    decltype(&ncclCommInitAll) init_all = nullptr;
-    decltype(&ncclBroadcast) broadcast = nullptr;
-    decltype(&ncclGroupStart) group_start = nullptr;
-    decltype(&ncclGroupEnd) group_end = nullptr;
-    decltype(&ncclCommDestroy) comm_destroy = nullptr;
-    decltype(&ncclGetErrorString) error_string = nullptr;
-    std::vector<int> devices;  // rank -> device
-    std::vector<ncclComm_t> comms;
-    ~RcclComms() {
-        for (size_t r = 0; r < comms.size(); r++)
-            if (comms[r] && comm_destroy) {
-                (void)hipSetDevice(devices[r]);
-                (void)comm_destroy(comms[r]);
-            }
-        if (lib) dlclose(lib);
-    }
-};
-
-namespace {
-
-void check_nccl(const RcclComms &rc, ncclResult_t r, const char *what) {
-    if (r != ncclSuccess) fail("%s: %s", what, rc.error_string ? rc.error_string(r) : "RCCL error");
-}
-
-// the communicator over `devices` (rank 0 = the source's device), created once per context
-RcclComms &rccl_for(TfheMi355Context *m, const std::vector<int> &devices) {
-    if (m->rccl && m->rccl->devices == devices) return *m->rccl;
-    delete m->rccl;
-    m->rccl = nullptr;
-    auto rc = std::make_unique<RcclComms>();
-    rc->lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-    if (!rc->lib) rc->lib = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-    if (!rc->lib) fail("RCCL is not available for key replication (%s); TFHE_MI355_REPLICATE=copy uses peer copies",
-                       dlerror());
-    auto sym = [&](const char *name) {
-        void *f = dlsym(rc->lib, name);
-        if (!f) fail("librccl lacks %s", name);
-        return f;
-    };
-    rc->init_all = reinterpret_cast<decltype(rc->init_all)>(sym("ncclCommInitAll"));
-    rc->broadcast = reinterpret_cast<decltype(rc->broadcast)>(sym("ncclBroadcast"));
-    rc->group_start = reinterpret_cast<decltype(rc->group_start)>(sym("ncclGroupStart"));
-    rc->group_end = reinterpret_cast<decltype(rc->group_end)>(sym("ncclGroupEnd"));
-    rc->comm_destroy = reinterpret_cast<decltype(rc->comm_destroy)>(sym("ncclCommDestroy"));
-    rc->error_string = reinterpret_cast<decltype(rc->error_string)>(sym("ncclGetErrorString"));
-    rc->devices = devices;
-    rc->comms.assign(devices.size(), nullptr);
-    check_nccl(*rc, rc->init_all(rc->comms.data(), (int)devices.size(), devices.data()), "ncclCommInitAll");
-    m->rccl = rc.release();
-    return *m->rccl;
-}
-
-// TFHE_MI355_REPLICATE: "auto" (default), "rccl", "copy" ("fail": a replication failure, test hook)
-std::string replicate_mode() {
-    const char *e = std::getenv("TFHE_MI355_REPLICATE");
-    return e && *e ? std::string(e) : std::string("auto");
-}
-
-enum class KeyPart { Fourier, Ksk };
-
-// shard 0's key part -> every other shard (see above); the ready flags are the caller's business
-void replicate(TfheMi355Context *m, KeyPart part) {
-    auto &S = m->shards;
-    TfheMi355Context *src = S[0];
-    const size_t bytes = part == KeyPart::Fourier ? src->fourier_bsk_bytes() : src->ksk_len() * sizeof(uint64_t);
-    auto buffer = [&](TfheMi355Context *s) -> DeviceBuffer & { return part == KeyPart::Fourier ? s->fbsk : s->ksk; };
-    if (!buffer(src).ptr || buffer(src).bytes < bytes) fail("no key on the first device to replicate");
-    // distinct devices in order of first appearance (rank 0: the source's) and the shards on each
-    std::vector<int> devs;
-    std::vector<std::vector<size_t>> on;
-    for (size_t i = 0; i < S.size(); i++) {
-        const auto it = std::find(devs.begin(), devs.end(), S[i]->device);
-        if (it == devs.end()) {
-            devs.push_back(S[i]->device);
-            on.push_back({i});
-        } else {
-            on[it - devs.begin()].push_back(i);
-        }
-    }
-    for (size_t i = 1; i < S.size(); i++) {
-        check(hipSetDevice(S[i]->device), "hipSetDevice");
-        buffer(S[i]).reserve(bytes);
-    }
-    // the shard of each device that receives the broadcast: the first one on it (on the source's
-    // device: a second shard there, else the source itself, in place)
-    std::vector<size_t> holder(devs.size());
-    for (size_t r = 0; r < devs.size(); r++) holder[r] = r == 0 && on[0].size() > 1 ? on[0][1] : on[r][0];
-    const std::string mode = replicate_mode();
-    m->replicate_note.clear();
-    if (mode == "fail") fail("key replication failed (TFHE_MI355_REPLICATE=fail test hook)");
-    bool use_rccl = mode == "rccl" || (mode != "copy" && devs.size() > 1);
-    RcclComms *rcp = nullptr;
-    if (use_rccl) {
-        try {
-            rcp = &rccl_for(m, devs);
-        } catch (const Failure &e) {
-            if (mode == "rccl") throw;
-            // auto: librccl missing or its communicator refused -> the peer-copy path
-            m->replicate_note = std::string("RCCL unavailable, peer copies: ") + e.what();
-            use_rccl = false;
-        }
-    }
-    auto sync_all = [&] {
-        for (auto *s : S) {
-            check(hipSetDevice(s->device), "hipSetDevice");
-            check(hipStreamSynchronize(s->stream), "key replication sync");
-        }
-    };
-    check(hipSetDevice(src->device), "hipSetDevice");
-    check(hipStreamSynchronize(src->stream), "key source sync");
-    m->replication = use_rccl ? TFHE_MI355_REPLICATION_RCCL
-                     : devs.size() > 1 ? TFHE_MI355_REPLICATION_PEER_COPY : TFHE_MI355_REPLICATION_DEVICE_COPY;
-    if (use_rccl) {
-        RcclComms &rc = *rcp;
-        check_nccl(rc, rc.group_start(), "ncclGroupStart");
-        for (size_t r = 0; r < devs.size(); r++) {
-            check(hipSetDevice(devs[r]), "hipSetDevice");
-            TfheMi355Context *h = S[holder[r]];
-            const ncclResult_t e =
-                rc.broadcast(buffer(src).ptr, buffer(h).ptr, bytes, ncclUint8, 0, rc.comms[r], h->stream);
-            if (e != ncclSuccess) {
-                (void)rc.group_end();
-                check_nccl(rc, e, "ncclBroadcast");
-            }
-        }
-        check_nccl(rc, rc.group_end(), "ncclGroupEnd");
-    } else {
-        for (size_t r = 0; r < devs.size(); r++) {
-            if (holder[r] == 0) continue;
-            TfheMi355Context *h = S[holder[r]];
-            check(hipSetDevice(h->device), "hipSetDevice");
-            check(h->device == src->device
-                      ? hipMemcpyAsync(buffer(h).ptr, buffer(src).ptr, bytes, hipMemcpyDeviceToDevice, h->stream)
-                      : hipMemcpyPeerAsync(buffer(h).ptr, h->device, buffer(src).ptr, src->device, bytes, h->stream),
-                  "key peer copy");
-        }
-    }
-    sync_all();
-    for (size_t r = 0; r < devs.size(); r++)  // the other shards of each device: from its holder
-        for (size_t i : on[r]) {
-            if (i == 0 || i == holder[r]) continue;
-            check(hipSetDevice(S[i]->device), "hipSetDevice");
-            check(hipMemcpyAsync(buffer(S[i]).ptr, buffer(S[holder[r]]).ptr, bytes, hipMemcpyDeviceToDevice,
-                                 S[i]->stream),
-                  "key device copy");
-        }
-    if (part == KeyPart::Ksk)  // each shard repacks its own byte planes for the MFMA keyswitch
-        for (size_t i = 1; i < S.size(); i++) {
-            check(hipSetDevice(S[i]->device), "hipSetDevice");
-            repack_ksk(S[i], S[i]->stream);
-        }
-    sync_all();
-    check(hipSetDevice(src->device), "hipSetDevice");
-}
-
-// the context itself, or the first shard of a multi-device one (device-pointer calls)
-TfheMi355Context *primary(TfheMi355Context *c) { return c && c->multi() ? c->shards[0] : c; }
-
-// the shard that takes the next small call / submitted request
-TfheMi355Context *pick_shard(TfheMi355Context *m) {
-    return m->shards[m->next_shard.fetch_add(1, std::memory_order_relaxed) % m->shards.size()];
-}
-
-// key writes of a multi-device context: its own lock (uploads in turn), then every shard's (no
-// coalesced batch on any device while the key changes)
-std::vector<std::unique_ptr<KeyWrite>> key_write_all(TfheMi355Context *c) {
-    std::vector<std::unique_ptr<KeyWrite>> w;
-    w.emplace_back(new KeyWrite(c));
-    for (auto *s : c->shards) w.emplace_back(new KeyWrite(s));
-    return w;
-}
-
-void set_ready_all(TfheMi355Context *m, KeyPart part, bool ready) {
-    for (auto *s : m->shards) {
-        if (part == KeyPart::Fourier) s->fbsk_ready = ready;
-        else s->ksk_ready = ready;
-    }
-}
-
-// a batched host-pointer call of a multi-device context: shard i runs rows [count i / S, count (i+1)
-// / S) through `f(shard, first, count)` (an entry point of the shard, 0 = ok), shard 0 on the calling
-// thread and the others on threads of their own; joined, then the first failure is reported
-// The whole call holds the multi-device context's key lock shared, so a concurrent key upload
-// (key_write_all: this context exclusively first) lands before or after it, never between two
-// shards' shares.
-template <class F>
-void split_rows(TfheMi355Context *m, size_t count, F &&f) {
-    const size_t S = m->shards.size();
-    KeyRead keys(m);
-    std::vector<std::string> errs(S);
-    auto run = [&](size_t i) {
-        const size_t a = count * i / S, b = count * (i + 1) / S;
-        if (a == b) return;
-        try {
-            if (f(m->shards[i], a, b - a) != TFHE_MI355_OK) errs[i] = tfhe_mi355_last_error();
-        } catch (const std::exception &e) {
-            errs[i] = e.what();
-        }
-    };
-    std::mutex dm;
-    std::condition_variable dcv;
-    size_t left = 0;
-    for (size_t i = 1; i < S; i++) {
-        if (count * i / S == count * (i + 1) / S) continue;
-        left++;
-        m->workers[i - 1]->post([&, i] {
-            run(i);
-            std::lock_guard<std::mutex> g(dm);
-            if (--left == 0) dcv.notify_one();
-        });
-    }
-    run(0);
-    {
-        std::unique_lock<std::mutex> g(dm);
-        dcv.wait(g, [&] { return left == 0; });
-    }
-    for (size_t i = 0; i < S; i++)
-        if (!errs[i].empty()) fail("device %d (shard %zu): %s", m->shards[i]->device, i, errs[i].c_str());
-}
-
-// peer access between every two distinct devices of a multi-device context, so that the peer-copy
-// replication (TFHE_MI355_REPLICATE=copy, or auto without RCCL) is a direct xGMI copy rather than
-// a staged one; a pair the platform cannot map keeps the staged path (not an error)
-void enable_peer_access(const std::vector<int> &devs) {
-    std::vector<int> d = devs;
-    std::sort(d.begin(), d.end());
-    d.erase(std::unique(d.begin(), d.end()), d.end());
-    for (int a : d)
-        for (int b : d) {
-            if (a == b) continue;
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, a, b) != hipSuccess || !can) continue;
-            if (hipSetDevice(a) != hipSuccess) continue;
-            (void)hipDeviceEnablePeerAccess(b, 0);  // hipErrorPeerAccessAlreadyEnabled is fine too
-            (void)hipGetLastError();                 // ... and leaves its code behind
-        }
-}
 
 // parameter checks shared by the single- and multi-device constructors
 void validate_parameters(const TfheMi355Parameters &p) {
@@ -2134,7 +1603,7 @@ TfheMi355Context *create_single(const TfheMi355Parameters &p, int device) {
     }
     return c;
 }
-}  // namespace
+}  // namespace tfhe_mi355::capi
 
 // key transaction of serde.cpp's serialized-key uploads (engine.h)
 std::shared_ptr<void> tfhe_mi355::begin_key_transaction(TfheMi355Context *ctx) {
@@ -2307,94 +1776,11 @@ int tfhe_mi355_context_create(const TfheMi355Parameters *params, int device, Tfh
     });
 }
 
-int tfhe_mi355_context_create_devices(const TfheMi355Parameters *params, const int *devices, size_t device_count,
-                                      TfheMi355Context **out_ctx) {
-    return guarded([&] {
-        if (!out_ctx) fail("null out_ctx");
-        *out_ctx = nullptr;
-        if (!params || (!devices && device_count)) fail("null argument");
-        validate_parameters(*params);
-        int visible = 0;
-        check(hipGetDeviceCount(&visible), "hipGetDeviceCount");
-        std::vector<int> devs(devices, devices + device_count);
-        if (devs.empty())  // no list: every visible device
-            for (int d = 0; d < visible; d++) devs.push_back(d);
-        if (devs.empty()) fail("no GPU visible");
-        if (devs.size() > 64) fail("at most 64 devices per context (%zu listed)", devs.size());
-        for (int d : devs)
-            if (d < 0 || d >= visible) fail("device %d is not visible (%d devices)", d, visible);
-        if (devs.size() == 1) {
-            *out_ctx = create_single(*params, devs[0]);
-            return;
-        }
-        auto *m = new TfheMi355Context();
-        m->p = *params;
-        m->device = devs[0];
-        try {
-            for (int d : devs) {
-                m->shards.push_back(create_single(*params, d));
-                m->shards.back()->owner = m;
-            }
-            for (size_t i = 1; i < devs.size(); i++) {
-                m->workers.emplace_back(new ShardWorker());
-                ShardWorker *w = m->workers.back().get();
-                w->t = std::thread([w] { w->loop(); });
-            }
-            enable_peer_access(devs);
-        } catch (...) {
-            tfhe_mi355_context_destroy(m);
-            throw;
-        }
-        *out_ctx = m;
-    });
-}
-
-int tfhe_mi355_context_devices(TfheMi355Context *ctx, size_t *count) {
-    return guarded([&] {
-        if (!ctx || !count) fail("null argument");
-        *count = ctx->multi() ? ctx->shards.size() : 1;
-    });
-}
-
-int tfhe_mi355_context_replication(TfheMi355Context *ctx, int *mode, const char **note) {
-    return guarded([&] {
-        if (!ctx || !mode) fail("null argument");
-        *mode = ctx->multi() ? ctx->replication : TFHE_MI355_REPLICATION_NONE;
-        if (note) *note = ctx->replicate_note.c_str();
-    });
-}
-
-int tfhe_mi355_context_device_context(TfheMi355Context *ctx, size_t index, TfheMi355Context **out_ctx,
-                                      int *device) {
-    return guarded([&] {
-        if (!out_ctx) fail("null out_ctx");
-        *out_ctx = nullptr;
-        if (!ctx) fail("null ctx");
-        const size_t n = ctx->multi() ? ctx->shards.size() : 1;
-        if (index >= n) fail("device index %zu out of range (%zu devices)", index, n);
-        TfheMi355Context *s = ctx->multi() ? ctx->shards[index] : ctx;
-        if (device) *device = s->device;
-        *out_ctx = s;
-    });
-}
-
 int tfhe_mi355_context_destroy(TfheMi355Context *ctx) {
     return guarded([&] {
         if (!ctx) return;
         if (ctx->owner) fail("this context belongs to a multi-device context: destroy that one");
-        if (ctx->multi()) {  // every shard (each reports its own queued requests), then the communicator
-            ctx->workers.clear();  // joins the shard workers (a split call still running finishes first)
-            std::string errs;
-            for (auto *s : ctx->shards) {
-                s->owner = nullptr;
-                if (tfhe_mi355_context_destroy(s) != TFHE_MI355_OK)
-                    errs += std::string(errs.empty() ? "" : "; ") + tfhe_mi355_last_error();
-            }
-            delete ctx->rccl;
-            delete ctx;
-            if (!errs.empty()) fail("%s", errs.c_str());
-            return;
-        }
+        if (ctx->multi()) return destroy_multi(ctx);
         (void)hipSetDevice(ctx->device);
         // 1. The coalescer first: take every still-queued request out of the queues and stop the
         //    dispatchers (a batch already running completes; its callers get their rows), join
@@ -2456,28 +1842,6 @@ int tfhe_mi355_context_destroy(TfheMi355Context *ctx) {
                  orphans.size());
     });
 }
-
-}  // extern "C"
-
-namespace {
-// a key upload of a multi-device context: `first` (the same entry point) on the first device's
-// shard, then the key part replicated to the other shards (RCCL broadcast / device copies)
-template <class F>
-void multi_key_upload(TfheMi355Context *m, KeyPart part, F &&first) {
-    auto w = key_write_all(m);
-    set_ready_all(m, part, false);
-    try {
-        abi(first(m->shards[0]));
-        replicate(m, part);
-    } catch (...) {  // the first shard may hold the new key already: no shard serves a half-replicated one
-        set_ready_all(m, part, false);
-        throw;
-    }
-    set_ready_all(m, part, true);
-}
-}  // namespace
-
-extern "C" {
 
 int tfhe_mi355_bootstrap_key_upload(TfheMi355Context *ctx, const uint64_t *bsk, size_t len) {
     return guarded([&] {
@@ -3277,7 +2641,7 @@ int tfhe_mi355_vertical_packing(TfheMi355Context *ctx, const uint64_t *ggsw_list
     });
 }
 
-// ---- WoP-PBS, the bootstrapped half ------------------------------------------------------------------
+// ---- WoP-PBS, the bootstrapped half: entry points -----------------------------------------------------
 
 int tfhe_mi355_pfpksk_list_upload(TfheMi355Context *ctx, const uint64_t *pfpksk, size_t len, uint32_t base_log,
                                   uint32_t level) {
@@ -3324,12 +2688,15 @@ void chunk_pfpks(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint
                  size_t n, void *sc, size_t sb, hipStream_t s) {
     launch_pfpks_dev(c, i, o, n, sc, sb, s);
 }
+}  // namespace
 
+namespace tfhe_mi355::capi {
 // host-pointer form of a WoP-PBS call: items in chunks through device buffers of the call's own, on
 // the context's stream; f(d_in, d_out, d_idx, n, d_scratch, scratch_bytes, stream) launches one chunk
-template <class Scratch, class F>
 void host_wop_call(TfheMi355Context *ctx, const uint64_t *in, size_t in_words, uint64_t *out, size_t out_words,
-                   const uint32_t *idx, size_t count, size_t chunk, Scratch &&scratch_bytes, F &&f) {
+                   const uint32_t *idx, size_t count, size_t chunk, const std::function<size_t(size_t)> &scratch_bytes,
+                   const std::function<void(const uint64_t *, uint64_t *, const uint32_t *, size_t, void *, size_t,
+                                            hipStream_t)> &f) {
     if (count == 0) return;
     chunk = std::min(count, std::max<size_t>(chunk, 1));
     DeviceBuffer d_in, d_out, d_idx, d_scr;
@@ -3347,8 +2714,7 @@ void host_wop_call(TfheMi355Context *ctx, const uint64_t *in, size_t in_words, u
         check(hipStreamSynchronize(s), "WoP-PBS sync");
     }
 }
-constexpr size_t kWopChunkRows = 4096;  // PBS rows per chunk of the host-pointer forms
-}  // namespace
+}  // namespace tfhe_mi355::capi
 
 extern "C" {
 
@@ -3604,8 +2970,7 @@ int tfhe_mi355_lwe_keyswitch_key_create(TfheMi355Context *ctx, const uint64_t *k
                  level);
         if (len != in_dim * level * (out_dim + 1))
             fail("keyswitching key has %zu words, expected %zu", len, in_dim * level * (out_dim + 1));
-        static const bool no_mfma = env_flag("TFHE_MI355_KS_NO_MFMA");
-        const bool mfma = !no_mfma && ks_mfma_supported((int)in_dim, (int)level, (int)base_log);
+        const bool mfma = !ks_mfma_disabled() && ks_mfma_supported((int)in_dim, (int)level, (int)base_log);
         if (!mfma && !keyswitch_scalar_supported((int)base_log, (int)level))
             fail("keyswitching key: no kernel for base_log %u x level %u (base_log <= 15, level <= 16)", base_log, level);
         std::unique_ptr<TfheMi355KeyswitchKey> k(new TfheMi355KeyswitchKey);
@@ -3860,814 +3225,6 @@ int tfhe_mi355_fill_accumulator(const TfheMi355Parameters *params, const uint64_
         for (size_t j = 0; j < half; j++) body[j] = 0 - body[j];
         std::memset(acc, 0, sizeof(uint64_t) * k * N);
         for (size_t j = 0; j < N; j++) acc[k * N + j] = body[(j + half) % N];
-    });
-}
-
-}  // extern "C"
-
-// ---- 32-bit torus (include/tfhe_mi355.h "32-bit torus") ------------------------------------------
-namespace {
-
-void require_single32(const TfheMi355Context *c) {
-    if (!c) fail("null ctx");
-    if (c->multi()) fail("32-bit-torus calls are not available on a multi-device context");
-}
-
-void require_shape32(const TfheMi355Context *c) {
-    const TfheMi355Parameters &p = c->p;
-    if (p.grouping_factor || !classic_pbs32_supported((int)p.polynomial_size, (int)p.glwe_dimension, (int)p.pbs_level))
-        fail("no 32-bit-torus PBS kernel for N=%u k=%u pbs_level=%u grouping_factor=%u", p.polynomial_size,
-             p.glwe_dimension, p.pbs_level, p.grouping_factor);
-    if (p.pbs_base_log < 2 || p.pbs_base_log * p.pbs_level > 30)
-        fail("32-bit-torus pbs decomposition: base_log >= 2 and base_log*level <= 30 (got %u x %u)", p.pbs_base_log,
-             p.pbs_level);
-}
-
-void require_ks_shape32(const TfheMi355Context *c) {
-    if (!keyswitch32_scalar_supported((int)c->p.ks_base_log, (int)c->p.ks_level))
-        fail("32-bit-torus ks decomposition: base_log*level <= 30, base_log <= 15, level <= 16 (got %u x %u)",
-             c->p.ks_base_log, c->p.ks_level);
-}
-
-void require_fbsk32(const TfheMi355Context *c) {
-    require_width32(c);
-    if (!c->fbsk32_ready) fail("32-bit-torus bootstrapping key not uploaded");
-}
-void require_ksk32(const TfheMi355Context *c) {
-    require_width32(c);
-    if (!c->ksk32_ready) fail("32-bit-torus keyswitching key not uploaded");
-}
-void require_order(int pbs_order) {
-    if (pbs_order != 0 && pbs_order != 1) fail("pbs_order must be 0 (KeyswitchBootstrap) or 1 (BootstrapKeyswitch)");
-}
-
-bool ks32_use_mfma(const TfheMi355Context *c) {
-    static const bool disabled = env_flag("TFHE_MI355_KS_NO_MFMA");
-    return !disabled && ks32_mfma_supported((int)c->big_dim(), (int)c->p.ks_level, (int)c->p.ks_base_log);
-}
-size_t ks32_scratch_bytes(const TfheMi355Context *c, size_t count) {
-    return ks32_use_mfma(c) && count ? ks32_mfma_scratch_bytes((int)c->big_dim(), (int)c->p.ks_level, (int)count) : 0;
-}
-// the u32 PBS kernel covers the batch in one pass: no ticket, no scratch
-size_t pbs32_scratch_bytes(const TfheMi355Context *, size_t) { return 0; }
-
-void launch_pbs32_dev(TfheMi355Context *c, const uint32_t *d_in, uint32_t *d_out, const uint32_t *d_luts,
-                      size_t lut_count, const uint32_t *d_idx, size_t count, hipStream_t s, bool glwe_out) {
-    if (count == 0) return;
-    require_fbsk32(c);
-    if (lut_count == 0) fail("lut_count must be >= 1");
-    if (lut_count > 0xffffffffu) fail("lut_count too large");
-    if (count > 0x7fffffff) fail("batch too large");
-    ClassicPbs32Launch a;
-    a.lwe_in = d_in;
-    a.lwe_out = d_out;
-    a.luts = d_luts;
-    a.lut_indexes = d_idx;
-    a.lut_count = (uint32_t)lut_count;
-    a.fbsk = reinterpret_cast<const double2 *>(c->fbsk.ptr);
-    a.W = c->tables.W;
-    a.twist = c->tables.twist;
-    a.n = (int)c->n();
-    a.base_log = (int)c->p.pbs_base_log;
-    a.count = (int)count;
-    a.glwe_out = glwe_out;
-    TimedLaunch tl(c->timer_or_null(), "pbs_classic32_kernel", s);
-    check(launch_classic_pbs32((int)c->N(), (int)c->k(), (int)c->p.pbs_level, a, s), "launch u32 pbs");
-}
-
-void launch_ks32_dev(TfheMi355Context *c, const uint32_t *d_in, uint32_t *d_out, size_t count, void *scratch,
-                     size_t scratch_bytes, hipStream_t s) {
-    if (count == 0) return;
-    require_ksk32(c);
-    if (count > 0x7fffffffu) fail("count too large");
-    Keyswitch32Launch a;
-    a.lwe_in = d_in;
-    a.lwe_out = d_out;
-    a.ksk = reinterpret_cast<const uint32_t *>(c->ksk32.ptr);
-    a.in_dim = (int)c->big_dim();
-    a.out_dim = (int)c->n();
-    a.base_log = (int)c->p.ks_base_log;
-    a.level = (int)c->p.ks_level;
-    a.count = (int)count;
-    TimedLaunch tl(c->timer_or_null(), "keyswitch32", s);
-    if (c->ksk32_planes_ready) {
-        require_scratch(scratch ? scratch_bytes : 0, ks32_scratch_bytes(c, count));
-        check(launch_keyswitch32_mfma(a, (const int8_t *)c->ksk32_planes.ptr, scratch, s), "launch u32 mfma keyswitch");
-        return;
-    }
-    check(launch_keyswitch32(a, s), "launch u32 keyswitch");
-}
-
-// gates: [prologue rows | other-side rows | keyswitch scratch]
-struct Gates32Layout {
-    size_t in_words, mid_words, a_bytes, b_bytes, ks_bytes;
-    size_t total() const { return a_bytes + b_bytes + ks_bytes; }
-};
-Gates32Layout gates32_layout(const TfheMi355Context *c, size_t count, int pbs_order) {
-    Gates32Layout l;
-    l.in_words = (pbs_order ? c->n() : c->big_dim()) + 1;
-    l.mid_words = (pbs_order ? c->big_dim() : c->n()) + 1;
-    l.a_bytes = align256(count * l.in_words * sizeof(uint32_t));
-    l.b_bytes = align256(count * l.mid_words * sizeof(uint32_t));
-    l.ks_bytes = ks32_scratch_bytes(c, count);
-    return l;
-}
-
-void launch_gates32_dev(TfheMi355Context *c, const uint8_t *d_ops, const uint32_t *d_lhs, const uint32_t *d_rhs,
-                        uint32_t *d_out, size_t count, int pbs_order, void *scratch, size_t scratch_bytes,
-                        hipStream_t s) {
-    if (count == 0) return;
-    require_fbsk32(c);
-    require_ksk32(c);
-    if (count > 0x3fffffffu) fail("count too large");
-    const Gates32Layout l = gates32_layout(c, count, pbs_order);
-    require_scratch(scratch ? scratch_bytes : 0, l.total());
-    uint32_t *a = reinterpret_cast<uint32_t *>(scratch);
-    uint32_t *b = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(scratch) + l.a_bytes);
-    void *ks = reinterpret_cast<char *>(scratch) + l.a_bytes + l.b_bytes;
-    const uint32_t *lut = reinterpret_cast<const uint32_t *>(c->lut_true32.ptr);
-    {
-        TimedLaunch tl(c->timer_or_null(), "boolean_ops", s);
-        check(launch_bool_gates_prologue(d_ops, d_lhs, d_rhs, a, count, l.in_words, s), "gate prologue");
-    }
-    if (pbs_order) {  // bootstrap_keyswitch (bootstrapping.rs:299-344)
-        launch_pbs32_dev(c, a, b, lut, 1, nullptr, count, s, false);
-        launch_ks32_dev(c, b, d_out, count, ks, l.ks_bytes, s);
-    } else {  // keyswitch_bootstrap (bootstrapping.rs:346-391)
-        launch_ks32_dev(c, a, b, count, ks, l.ks_bytes, s);
-        launch_pbs32_dev(c, b, d_out, lut, 1, nullptr, count, s, false);
-    }
-}
-
-// mux: [2 count rows | 2 count rows | count big rows | keyswitch scratch (2 count rows)]
-struct Mux32Layout {
-    size_t in_words, a_bytes, c_bytes, ks_bytes;
-    size_t total() const { return 2 * a_bytes + c_bytes + ks_bytes; }
-};
-Mux32Layout mux32_layout(const TfheMi355Context *c, size_t count, int pbs_order) {
-    Mux32Layout l;
-    l.in_words = (pbs_order ? c->n() : c->big_dim()) + 1;
-    l.a_bytes = align256(2 * count * (std::max(c->n(), c->big_dim()) + 1) * sizeof(uint32_t));
-    l.c_bytes = align256(count * (c->big_dim() + 1) * sizeof(uint32_t));
-    l.ks_bytes = ks32_scratch_bytes(c, 2 * count);
-    return l;
-}
-
-void launch_mux32_dev(TfheMi355Context *c, const uint32_t *d_cond, const uint32_t *d_then, const uint32_t *d_else,
-                      uint32_t *d_out, size_t count, int pbs_order, void *scratch, size_t scratch_bytes,
-                      hipStream_t s) {
-    if (count == 0) return;
-    require_fbsk32(c);
-    require_ksk32(c);
-    if (count > 0x1fffffffu) fail("count too large");
-    const Mux32Layout l = mux32_layout(c, count, pbs_order);
-    require_scratch(scratch ? scratch_bytes : 0, l.total());
-    char *base = reinterpret_cast<char *>(scratch);
-    uint32_t *a = reinterpret_cast<uint32_t *>(base);
-    uint32_t *b = reinterpret_cast<uint32_t *>(base + l.a_bytes);
-    uint32_t *sum = reinterpret_cast<uint32_t *>(base + 2 * l.a_bytes);
-    void *ks = base + 2 * l.a_bytes + l.c_bytes;
-    const uint32_t *lut = reinterpret_cast<const uint32_t *>(c->lut_true32.ptr);
-    const size_t big = c->big_dim() + 1;
-    {
-        TimedLaunch tl(c->timer_or_null(), "boolean_ops", s);
-        check(launch_bool_mux_prologue(d_cond, d_then, d_else, a, count, l.in_words, s), "mux prologue");
-    }
-    if (pbs_order) {  // mod.rs:548-565: two bootstraps, the sum, then one keyswitch
-        launch_pbs32_dev(c, a, b, lut, 1, nullptr, 2 * count, s, false);
-        {
-            TimedLaunch tl(c->timer_or_null(), "boolean_ops", s);
-            check(launch_bool_mux_epilogue(b, sum, count, big, s), "mux epilogue");
-        }
-        launch_ks32_dev(c, sum, d_out, count, ks, l.ks_bytes, s);
-    } else {  // mod.rs:530-547: keyswitch and bootstrap each row, then the sum
-        launch_ks32_dev(c, a, b, 2 * count, ks, l.ks_bytes, s);
-        launch_pbs32_dev(c, b, a, lut, 1, nullptr, 2 * count, s, false);
-        TimedLaunch tl(c->timer_or_null(), "boolean_ops", s);
-        check(launch_bool_mux_epilogue(a, d_out, count, big, s), "mux epilogue");
-    }
-}
-
-// A host-pointer u32 call: under the context's mutex, inputs staged into lane 0's device buffer, the
-// kernels on the context's stream, the output copied back after them.
-struct HostCall32 {
-    TfheMi355Context *c;
-    std::lock_guard<std::mutex> g;
-    size_t in_off = 0;
-    HostCall32(TfheMi355Context *c_, size_t in_bytes, size_t out_bytes, size_t scratch_bytes) : c(c_), g(c_->mu) {
-        check(hipSetDevice(c->device), "hipSetDevice");
-        c->lanes[0].d_in.reserve(std::max<size_t>(in_bytes, 256));
-        c->lanes[0].d_out.reserve(std::max<size_t>(out_bytes, 256));
-        c->io_tmp.reserve(std::max<size_t>(scratch_bytes, 256));
-    }
-    template <class T>
-    const T *up(const T *host, size_t n) {
-        if (!host || n == 0) return nullptr;
-        char *d = reinterpret_cast<char *>(c->lanes[0].d_in.ptr) + in_off;
-        check(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, c->stream), "H2D");
-        in_off += align256(n * sizeof(T));
-        return reinterpret_cast<const T *>(d);
-    }
-    uint32_t *out() { return reinterpret_cast<uint32_t *>(c->lanes[0].d_out.ptr); }
-    void *scratch() { return c->io_tmp.ptr; }
-    void down(uint32_t *host, size_t n) {
-        check(hipMemcpyAsync(host, out(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream), "D2H");
-        check(hipStreamSynchronize(c->stream), "u32 call sync");
-    }
-};
-
-void pbs32_host(TfheMi355Context *ctx, const uint32_t *lwe_in, uint32_t *out, const uint32_t *luts, size_t lut_count,
-                const uint32_t *lut_indexes, size_t count, bool glwe_out) {
-    require_single32(ctx);
-    if ((!lwe_in && count) || (!out && count) || !luts) fail("null argument");
-    if (count == 0) return;
-    require_fbsk32(ctx);
-    if (lut_count == 0) fail("lut_count must be >= 1");
-    validate_lut_indexes(lut_indexes, count, lut_count);
-    const size_t wi = ctx->n() + 1, wo = glwe_out ? ctx->glwe_len() : ctx->big_dim() + 1;
-    HostCall32 h(ctx, align256(count * wi * 4) + align256(lut_count * ctx->glwe_len() * 4) + align256(count * 4),
-                 count * wo * 4, 0);
-    const uint32_t *d_in = h.up(lwe_in, count * wi);
-    const uint32_t *d_luts = h.up(luts, lut_count * ctx->glwe_len());
-    const uint32_t *d_idx = h.up(lut_indexes, lut_indexes ? count : 0);
-    launch_pbs32_dev(ctx, d_in, h.out(), d_luts, lut_count, d_idx, count, ctx->stream, glwe_out);
-    h.down(out, count * wo);
-}
-
-}  // namespace
-
-extern "C" {
-
-int tfhe_mi355_bootstrap_key_upload_u32(TfheMi355Context *ctx, const uint32_t *bsk, size_t len) {
-    return guarded([&] {
-        require_single32(ctx);
-        if (!bsk) fail("null argument");
-        KeyWrite kw(ctx);
-        require_width32(ctx);
-        require_shape32(ctx);
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        if (len != ctx->std_bsk_len()) fail("bootstrapping key has %zu words, expected %zu", len, ctx->std_bsk_len());
-        ctx->fbsk32_ready = false;
-        // [u32 key | the same words widened to u64], converted by the u64 path's kernel
-        const size_t wide_off = align256(len * sizeof(uint32_t));
-        ctx->std_staging.reserve(wide_off + len * sizeof(uint64_t));
-        const uint32_t *d32 = reinterpret_cast<const uint32_t *>(ctx->std_staging.ptr);
-        uint64_t *d64 = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->std_staging.ptr) + wide_off);
-        check(hipMemcpyAsync(ctx->std_staging.ptr, bsk, len * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream),
-              "upload u32 bsk");
-        check(launch_widen32(d32, d64, len, ctx->stream), "widen u32 bsk");
-        ctx->fbsk.reserve(ctx->fourier_bsk_bytes());
-        check(launch_bsk_to_fourier((int)ctx->N(), d64, (double2 *)ctx->fbsk.ptr, len / ctx->N(), ctx->tables,
-                                    ctx->stream),
-              "u32 bsk conversion");
-        // the gates' accumulator (bootstrapping.rs:59-60): zero mask, body all PLAINTEXT_TRUE
-        std::vector<uint32_t> lut(ctx->glwe_len(), 0u);
-        for (size_t j = ctx->big_dim(); j < ctx->glwe_len(); j++) lut[j] = 1u << 29;
-        ctx->lut_true32.reserve(lut.size() * sizeof(uint32_t));
-        check(hipMemcpyAsync(ctx->lut_true32.ptr, lut.data(), lut.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                             ctx->stream),
-              "upload gate accumulator");
-        check(hipStreamSynchronize(ctx->stream), "u32 bsk conversion sync");
-        ctx->std_staging.release();
-        ctx->fbsk32_ready = true;
-    });
-}
-
-int tfhe_mi355_keyswitch_key_upload_u32(TfheMi355Context *ctx, const uint32_t *ksk, size_t len) {
-    return guarded([&] {
-        require_single32(ctx);
-        if (!ksk) fail("null argument");
-        KeyWrite kw(ctx);
-        require_width32(ctx);
-        require_ks_shape32(ctx);
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        if (len != ctx->ksk_len()) fail("keyswitching key has %zu words, expected %zu", len, ctx->ksk_len());
-        ctx->ksk32_ready = ctx->ksk32_planes_ready = false;
-        ctx->ksk32.reserve(len * sizeof(uint32_t));
-        check(hipMemcpyAsync(ctx->ksk32.ptr, ksk, len * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream),
-              "upload u32 ksk");
-        if (ks32_use_mfma(ctx)) {  // four int8 byte planes, once per key
-            ctx->ksk32_planes.reserve(4 * ks_mfma_rows((int)ctx->big_dim(), (int)ctx->p.ks_level) *
-                                      ks_mfma_cols((int)ctx->n()));
-            check(launch_ksk32_repack((const uint32_t *)ctx->ksk32.ptr, (int8_t *)ctx->ksk32_planes.ptr,
-                                      (int)ctx->big_dim(), (int)ctx->p.ks_level, (int)ctx->n(), ctx->stream),
-                  "u32 ksk repack");
-        }
-        check(hipStreamSynchronize(ctx->stream), "u32 ksk upload sync");
-        ctx->ksk32_planes_ready = ks32_use_mfma(ctx);
-        ctx->ksk32_ready = true;
-    });
-}
-
-int tfhe_mi355_programmable_bootstrap_u32(TfheMi355Context *ctx, const uint32_t *lwe_in, uint32_t *lwe_out,
-                                          const uint32_t *luts, size_t lut_count, const uint32_t *lut_indexes,
-                                          size_t count) {
-    return guarded([&] { pbs32_host(ctx, lwe_in, lwe_out, luts, lut_count, lut_indexes, count, false); });
-}
-
-int tfhe_mi355_blind_rotate_u32(TfheMi355Context *ctx, const uint32_t *lwe_in, uint32_t *glwe_out,
-                                const uint32_t *luts, size_t lut_count, const uint32_t *lut_indexes, size_t count) {
-    return guarded([&] { pbs32_host(ctx, lwe_in, glwe_out, luts, lut_count, lut_indexes, count, true); });
-}
-
-int tfhe_mi355_programmable_bootstrap_u32_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes) {
-    return guarded([&] {
-        require_single32(ctx);
-        if (!bytes) fail("null argument");
-        *bytes = pbs32_scratch_bytes(ctx, count);
-    });
-}
-
-int tfhe_mi355_blind_rotate_u32_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes) {
-    return tfhe_mi355_programmable_bootstrap_u32_scratch(ctx, count, bytes);
-}
-
-int tfhe_mi355_programmable_bootstrap_u32_async(TfheMi355Context *ctx, const uint32_t *d_in, uint32_t *d_out,
-                                                const uint32_t *d_luts, size_t lut_count, const uint32_t *d_idx,
-                                                size_t count, void *d_scratch, size_t scratch_bytes, void *stream) {
-    return guarded([&] {
-        require_single32(ctx);
-        if ((!d_in && count) || (!d_out && count) || !d_luts) fail("null argument");
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        require_scratch(d_scratch ? scratch_bytes : 0, pbs32_scratch_bytes(ctx, count));
-        launch_pbs32_dev(ctx, d_in, d_out, d_luts, lut_count, d_idx, count, (hipStream_t)stream, false);
-    });
-}
-
-int tfhe_mi355_blind_rotate_u32_async(TfheMi355Context *ctx, const uint32_t *d_in, uint32_t *d_glwe_out,
-                                      const uint32_t *d_luts, size_t lut_count, const uint32_t *d_idx, size_t count,
-                                      void *d_scratch, size_t scratch_bytes, void *stream) {
-    return guarded([&] {
-        require_single32(ctx);
-        if ((!d_in && count) || (!d_glwe_out && count) || !d_luts) fail("null argument");
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        require_scratch(d_scratch ? scratch_bytes : 0, pbs32_scratch_bytes(ctx, count));
-        launch_pbs32_dev(ctx, d_in, d_glwe_out, d_luts, lut_count, d_idx, count, (hipStream_t)stream, true);
-    });
-}
-
-int tfhe_mi355_keyswitch_u32(TfheMi355Context *ctx, const uint32_t *lwe_in, uint32_t *lwe_out, size_t count) {
-    return guarded([&] {
-        require_single32(ctx);
-        if ((!lwe_in && count) || (!lwe_out && count)) fail("null argument");
-        if (count == 0) return;
-        require_ksk32(ctx);
-        const size_t wi = ctx->big_dim() + 1, wo = ctx->n() + 1;
-        const size_t sb = ks32_scratch_bytes(ctx, count);
-        HostCall32 h(ctx, align256(count * wi * 4), count * wo * 4, sb);
-        const uint32_t *d_in = h.up(lwe_in, count * wi);
-        launch_ks32_dev(ctx, d_in, h.out(), count, h.scratch(), sb, ctx->stream);
-        h.down(lwe_out, count * wo);
-    });
-}
-
-int tfhe_mi355_keyswitch_u32_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes) {
-    return guarded([&] {
-        require_single32(ctx);
-        if (!bytes) fail("null argument");
-        *bytes = ks32_scratch_bytes(ctx, count);
-    });
-}
-
-int tfhe_mi355_keyswitch_u32_async(TfheMi355Context *ctx, const uint32_t *d_in, uint32_t *d_out, size_t count,
-                                   void *d_scratch, size_t scratch_bytes, void *stream) {
-    return guarded([&] {
-        require_single32(ctx);
-        if ((!d_in && count) || (!d_out && count)) fail("null argument");
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        launch_ks32_dev(ctx, d_in, d_out, count, d_scratch, scratch_bytes, (hipStream_t)stream);
-    });
-}
-
-int tfhe_mi355_boolean_gates(TfheMi355Context *ctx, const uint8_t *ops, const uint32_t *lhs, const uint32_t *rhs,
-                             uint32_t *out, size_t count, int pbs_order) {
-    return guarded([&] {
-        require_single32(ctx);
-        require_order(pbs_order);
-        if ((!ops || !lhs || !rhs || !out) && count) fail("null argument");
-        if (count == 0) return;
-        for (size_t i = 0; i < count; i++)
-            if (ops[i] > TFHE_MI355_GATE_XNOR) fail("ops[%zu] = %u is not a gate opcode (0..5)", i, (unsigned)ops[i]);
-        require_fbsk32(ctx);
-        require_ksk32(ctx);
-        const Gates32Layout l = gates32_layout(ctx, count, pbs_order);
-        const size_t words = count * l.in_words;
-        HostCall32 h(ctx, 2 * align256(words * 4) + align256(count), words * 4, l.total());
-        const uint32_t *d_lhs = h.up(lhs, words);
-        const uint32_t *d_rhs = h.up(rhs, words);
-        const uint8_t *d_ops = h.up(ops, count);
-        launch_gates32_dev(ctx, d_ops, d_lhs, d_rhs, h.out(), count, pbs_order, h.scratch(), l.total(), ctx->stream);
-        h.down(out, words);
-    });
-}
-
-int tfhe_mi355_boolean_gates_scratch(TfheMi355Context *ctx, size_t count, int pbs_order, size_t *bytes) {
-    return guarded([&] {
-        require_single32(ctx);
-        require_order(pbs_order);
-        if (!bytes) fail("null argument");
-        *bytes = count ? gates32_layout(ctx, count, pbs_order).total() : 0;
-    });
-}
-
-int tfhe_mi355_boolean_gates_async(TfheMi355Context *ctx, const uint8_t *d_ops, const uint32_t *d_lhs,
-                                   const uint32_t *d_rhs, uint32_t *d_out, size_t count, int pbs_order,
-                                   void *d_scratch, size_t scratch_bytes, void *stream) {
-    return guarded([&] {
-        require_single32(ctx);
-        require_order(pbs_order);
-        if ((!d_ops || !d_lhs || !d_rhs || !d_out) && count) fail("null argument");
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        launch_gates32_dev(ctx, d_ops, d_lhs, d_rhs, d_out, count, pbs_order, d_scratch, scratch_bytes,
-                           (hipStream_t)stream);
-    });
-}
-
-int tfhe_mi355_boolean_mux(TfheMi355Context *ctx, const uint32_t *cond, const uint32_t *then_ct,
-                           const uint32_t *else_ct, uint32_t *out, size_t count, int pbs_order) {
-    return guarded([&] {
-        require_single32(ctx);
-        require_order(pbs_order);
-        if ((!cond || !then_ct || !else_ct || !out) && count) fail("null argument");
-        if (count == 0) return;
-        require_fbsk32(ctx);
-        require_ksk32(ctx);
-        const Mux32Layout l = mux32_layout(ctx, count, pbs_order);
-        const size_t words = count * l.in_words;
-        HostCall32 h(ctx, 3 * align256(words * 4), words * 4, l.total());
-        const uint32_t *d_c = h.up(cond, words);
-        const uint32_t *d_t = h.up(then_ct, words);
-        const uint32_t *d_e = h.up(else_ct, words);
-        launch_mux32_dev(ctx, d_c, d_t, d_e, h.out(), count, pbs_order, h.scratch(), l.total(), ctx->stream);
-        h.down(out, words);
-    });
-}
-
-int tfhe_mi355_boolean_mux_scratch(TfheMi355Context *ctx, size_t count, int pbs_order, size_t *bytes) {
-    return guarded([&] {
-        require_single32(ctx);
-        require_order(pbs_order);
-        if (!bytes) fail("null argument");
-        *bytes = count ? mux32_layout(ctx, count, pbs_order).total() : 0;
-    });
-}
-
-int tfhe_mi355_boolean_mux_async(TfheMi355Context *ctx, const uint32_t *d_cond, const uint32_t *d_then,
-                                 const uint32_t *d_else, uint32_t *d_out, size_t count, int pbs_order,
-                                 void *d_scratch, size_t scratch_bytes, void *stream) {
-    return guarded([&] {
-        require_single32(ctx);
-        require_order(pbs_order);
-        if ((!d_cond || !d_then || !d_else || !d_out) && count) fail("null argument");
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        launch_mux32_dev(ctx, d_cond, d_then, d_else, d_out, count, pbs_order, d_scratch, scratch_bytes,
-                         (hipStream_t)stream);
-    });
-}
-
-int tfhe_mi355_boolean_not_async(TfheMi355Context *ctx, const uint32_t *d_in, uint32_t *d_out, size_t words,
-                                 void *stream) {
-    return guarded([&] {
-        require_single32(ctx);
-        if ((!d_in || !d_out) && words) fail("null argument");
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        TimedLaunch tl(ctx->timer_or_null(), "boolean_ops", (hipStream_t)stream);
-        check(launch_bool_negate(d_in, d_out, words, (hipStream_t)stream), "boolean not");
-    });
-}
-
-int tfhe_mi355_debug_torus32_from_fraction(int device, const double *fr, uint32_t *acc_inout, uint32_t *set_out,
-                                           size_t n) {
-    return guarded([&] {
-        if ((!fr || !acc_inout || !set_out) && n) fail("null argument");
-        if (n == 0) return;
-        check(hipSetDevice(device), "hipSetDevice");
-        DeviceBuffer d_fr, d_acc, d_set;
-        d_fr.reserve(n * sizeof(double));
-        d_acc.reserve(n * sizeof(uint32_t));
-        d_set.reserve(n * sizeof(uint32_t));
-        check(hipMemcpy(d_fr.ptr, fr, n * sizeof(double), hipMemcpyHostToDevice), "H2D fr");
-        check(hipMemcpy(d_acc.ptr, acc_inout, n * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D acc");
-        check(launch_torus32_from_fraction((const double *)d_fr.ptr, (uint32_t *)d_acc.ptr, (uint32_t *)d_set.ptr, n,
-                                           nullptr),
-              "torus32 conversion");
-        check(hipMemcpy(acc_inout, d_acc.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H acc");
-        check(hipMemcpy(set_out, d_set.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H set");
-    });
-}
-
-int tfhe_mi355_debug_keyswitch_u32(TfheMi355Context *ctx, const uint32_t *ksk, size_t in_dim, size_t out_dim,
-                                   uint32_t base_log, uint32_t level, int arm, const uint32_t *lwe_in,
-                                   uint32_t *lwe_out, size_t count) {
-    return guarded([&] {
-        require_single32(ctx);
-        if (!ksk || ((!lwe_in || !lwe_out) && count)) fail("null argument");
-        if (in_dim == 0 || out_dim == 0 || in_dim > (1u << 20) || out_dim > (1u << 20)) fail("dimension out of range");
-        if (count > (1u << 20)) fail("count too large");
-        if (base_log == 0 || level == 0 || base_log * level > 30) fail("ks decomposition: base_log*level <= 30");
-        const bool can_mfma = ks32_mfma_supported((int)in_dim, (int)level, (int)base_log);
-        const bool can_scalar = keyswitch32_scalar_supported((int)base_log, (int)level);
-        if (arm < 0 || arm > 2) fail("arm must be 0 (the engine's choice), 1 (integer) or 2 (int8 MFMA)");
-        if (arm == 2 && !can_mfma) fail("the int8-MFMA keyswitch does not take this shape");
-        if (arm == 1 && !can_scalar) fail("the integer keyswitch does not take this decomposition");
-        if (!can_mfma && !can_scalar) fail("no 32-bit keyswitch kernel for this decomposition");
-        const bool mfma = arm == 2 || (arm == 0 && can_mfma);
-        if (count == 0) return;
-        std::lock_guard<std::mutex> g(ctx->mu);
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        const size_t klen = in_dim * level * (out_dim + 1);
-        DeviceBuffer d_ksk, d_planes, d_in, d_out, d_scratch;
-        d_ksk.reserve(klen * 4);
-        d_in.reserve(count * (in_dim + 1) * 4);
-        d_out.reserve(count * (out_dim + 1) * 4);
-        check(hipMemcpyAsync(d_ksk.ptr, ksk, klen * 4, hipMemcpyHostToDevice, ctx->stream), "H2D ksk");
-        check(hipMemcpyAsync(d_in.ptr, lwe_in, count * (in_dim + 1) * 4, hipMemcpyHostToDevice, ctx->stream), "H2D");
-        Keyswitch32Launch a;
-        a.lwe_in = (const uint32_t *)d_in.ptr;
-        a.lwe_out = (uint32_t *)d_out.ptr;
-        a.ksk = (const uint32_t *)d_ksk.ptr;
-        a.in_dim = (int)in_dim;
-        a.out_dim = (int)out_dim;
-        a.base_log = (int)base_log;
-        a.level = (int)level;
-        a.count = (int)count;
-        if (mfma) {
-            d_planes.reserve(4 * ks_mfma_rows((int)in_dim, (int)level) * ks_mfma_cols((int)out_dim));
-            d_scratch.reserve(ks32_mfma_scratch_bytes((int)in_dim, (int)level, (int)count));
-            check(launch_ksk32_repack(a.ksk, (int8_t *)d_planes.ptr, a.in_dim, a.level, a.out_dim, ctx->stream),
-                  "u32 ksk repack");
-            TimedLaunch tl(ctx->timer_or_null(), "keyswitch32_mfma", ctx->stream);
-            check(launch_keyswitch32_mfma(a, (const int8_t *)d_planes.ptr, d_scratch.ptr, ctx->stream),
-                  "launch u32 mfma keyswitch");
-        } else {
-            TimedLaunch tl(ctx->timer_or_null(), "keyswitch32_integer", ctx->stream);
-            check(launch_keyswitch32(a, ctx->stream), "launch u32 keyswitch");
-        }
-        check(hipMemcpyAsync(lwe_out, d_out.ptr, count * (out_dim + 1) * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H");
-        check(hipStreamSynchronize(ctx->stream), "u32 keyswitch sync");
-    });
-}
-
-int tfhe_mi355_debug_pbs_u32_resident(TfheMi355Context *ctx, size_t *count) {
-    return guarded([&] {
-        require_single32(ctx);
-        if (!count) fail("null argument");
-        require_shape32(ctx);
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        *count = (size_t)classic_pbs32_resident_blocks((int)ctx->N(), (int)ctx->k(), (int)ctx->p.pbs_level);
-    });
-}
-
-
-}  // extern "C"
-
-// ---- 128-bit torus (pbs_f128.hip; the reference's fft128 path) ----------------------------------------
-namespace {
-
-typedef unsigned __int128 u128w;
-
-void require_single128(const TfheMi355Context *c) {
-    if (!c) fail("null ctx");
-    if (c->multi()) fail("128-bit-torus calls are not available on a multi-device context");
-}
-void require_width128(const TfheMi355Context *c) {
-    if (c->has_u64_keys()) fail("the context holds 64-bit-torus keys: 128-bit calls need a context of their own");
-    if (c->has_u32_keys()) fail("the context holds 32-bit-torus keys: 128-bit calls need a context of their own");
-}
-// every limit of the f128 kernel, named
-void validate_shape128(const TfheMi355Parameters &p) {
-    const uint32_t N = p.polynomial_size, k = p.glwe_dimension;
-    if (N != 256 && N != 512 && N != 1024 && N != 2048)
-        fail("128-bit-torus PBS: polynomial_size must be 256, 512, 1024 or 2048 (got %u)", N);
-    if (k < 1 || k > 3) fail("128-bit-torus PBS: glwe_dimension must be 1, 2 or 3 (got %u)", k);
-    if ((k + 1) * N > 4096) fail("128-bit-torus PBS: (k+1)*N must be <= 4096 (got %u)", (k + 1) * N);
-    if (p.pbs_level < 1 || p.pbs_level > 4) fail("128-bit-torus PBS: pbs_level must be in [1, 4] (got %u)", p.pbs_level);
-    if (p.pbs_base_log < 2 || p.pbs_base_log > 31)
-        fail("128-bit-torus PBS: pbs_base_log must be in [2, 31] (got %u)", p.pbs_base_log);
-    if (p.pbs_base_log * p.pbs_level >= 128)
-        fail("128-bit-torus PBS: pbs_base_log*pbs_level must be < 128 (got %u x %u)", p.pbs_base_log, p.pbs_level);
-    if (p.grouping_factor) fail("128-bit-torus PBS: no multi-bit variant (grouping_factor %u)", p.grouping_factor);
-    if (p.lwe_dimension == 0) fail("lwe_dimension must be > 0");
-    if (!pbs_f128_supported((int)N, (int)k)) fail("no 128-bit-torus PBS kernel for N=%u k=%u", N, k);
-}
-void require_modulus128(uint32_t m) {
-    if (m < 65 || m > 128) fail("128-bit-torus PBS: ciphertext_modulus_log must be in [65, 128] (got %u)", m);
-}
-void require_fbsk128(const TfheMi355Context *c) {
-    require_width128(c);
-    if (!c->fbsk128_ready) fail("128-bit-torus bootstrapping key not uploaded");
-}
-const double *twist128(const TfheMi355Context *c) { return reinterpret_cast<const double *>(c->tables128.ptr); }
-const double *tw128(const TfheMi355Context *c) { return twist128(c) + 2 * c->N(); }
-
-// the monomial degrees of the batch (one uint32_t per input word); everything else stays on chip
-size_t pbs128_scratch_bytes(const TfheMi355Context *c, size_t count) {
-    return count ? align256(count * (c->n() + 1) * sizeof(uint32_t)) : 0;
-}
-
-void launch_pbs128_dev(TfheMi355Context *c, const void *d_in, void *d_out, const void *d_luts, size_t lut_count,
-                       const uint32_t *d_idx, size_t count, uint32_t modulus_log, void *scratch, size_t scratch_bytes,
-                       hipStream_t s, bool glwe_out) {
-    require_modulus128(modulus_log);
-    if (count == 0) return;
-    require_fbsk128(c);
-    require_scratch(scratch ? scratch_bytes : 0, pbs128_scratch_bytes(c, count));
-    if (lut_count == 0) fail("lut_count must be >= 1");
-    if (lut_count > 0xffffffffu) fail("lut_count too large");
-    if (count > 0x7fffffff) fail("batch too large");
-    PbsF128Launch a;
-    a.lwe_in = reinterpret_cast<const u128w *>(d_in);
-    a.lwe_out = reinterpret_cast<u128w *>(d_out);
-    a.luts = reinterpret_cast<const u128w *>(d_luts);
-    a.lut_indexes = d_idx;
-    a.lut_count = (uint32_t)lut_count;
-    a.fbsk = reinterpret_cast<const double *>(c->fbsk128.ptr);
-    a.twist = twist128(c);
-    a.tw = tw128(c);
-    a.degrees = reinterpret_cast<uint32_t *>(scratch);
-    a.n = (int)c->n();
-    a.base_log = (int)c->p.pbs_base_log;
-    a.level = (int)c->p.pbs_level;
-    a.modulus_log = (int)modulus_log;
-    a.count = (int)count;
-    a.glwe_out = glwe_out;
-    TimedLaunch tl(c->timer_or_null(), "pbs_f128_kernel", s);
-    check(launch_pbs_f128((int)c->N(), (int)c->k(), a, s), "launch u128 pbs");
-}
-
-void pbs128_host(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *out, const uint64_t *luts, size_t lut_count,
-                 const uint32_t *lut_indexes, size_t count, uint32_t modulus_log, bool glwe_out) {
-    require_single128(ctx);
-    require_modulus128(modulus_log);
-    if ((!lwe_in && count) || (!out && count) || !luts) fail("null argument");
-    if (count == 0) return;
-    require_fbsk128(ctx);
-    if (lut_count == 0) fail("lut_count must be >= 1");
-    validate_lut_indexes(lut_indexes, count, lut_count);
-    const size_t wi = ctx->n() + 1, wo = glwe_out ? ctx->glwe_len() : ctx->big_dim() + 1;
-    const size_t in_b = align256(count * wi * 16), lut_b = align256(lut_count * ctx->glwe_len() * 16);
-    std::lock_guard<std::mutex> g(ctx->mu);
-    check(hipSetDevice(ctx->device), "hipSetDevice");
-    ctx->lanes[0].d_in.reserve(in_b + lut_b + align256(count * 4));
-    ctx->lanes[0].d_out.reserve(std::max<size_t>(count * wo * 16, 256));
-    const size_t sb = pbs128_scratch_bytes(ctx, count);
-    ctx->io_tmp.reserve(sb);
-    char *d = reinterpret_cast<char *>(ctx->lanes[0].d_in.ptr);
-    check(hipMemcpyAsync(d, lwe_in, count * wi * 16, hipMemcpyHostToDevice, ctx->stream), "H2D");
-    check(hipMemcpyAsync(d + in_b, luts, lut_count * ctx->glwe_len() * 16, hipMemcpyHostToDevice, ctx->stream), "H2D");
-    const uint32_t *d_idx = nullptr;
-    if (lut_indexes) {
-        check(hipMemcpyAsync(d + in_b + lut_b, lut_indexes, count * 4, hipMemcpyHostToDevice, ctx->stream), "H2D");
-        d_idx = reinterpret_cast<const uint32_t *>(d + in_b + lut_b);
-    }
-    launch_pbs128_dev(ctx, d, ctx->lanes[0].d_out.ptr, d + in_b, lut_count, d_idx, count, modulus_log,
-                      ctx->io_tmp.ptr, sb, ctx->stream, glwe_out);
-    check(hipMemcpyAsync(out, ctx->lanes[0].d_out.ptr, count * wo * 16, hipMemcpyDeviceToHost, ctx->stream), "D2H");
-    check(hipStreamSynchronize(ctx->stream), "u128 call sync");
-}
-
-void pbs128_async(TfheMi355Context *ctx, const void *d_in, void *d_out, const void *d_luts, size_t lut_count,
-                  const uint32_t *d_idx, size_t count, uint32_t modulus_log, void *d_scratch, size_t scratch_bytes,
-                  void *stream, bool glwe_out) {
-    require_single128(ctx);
-    if ((!d_in && count) || (!d_out && count) || !d_luts) fail("null argument");
-    check(hipSetDevice(ctx->device), "hipSetDevice");
-    launch_pbs128_dev(ctx, d_in, d_out, d_luts, lut_count, d_idx, count, modulus_log, d_scratch, scratch_bytes,
-                      (hipStream_t)stream, glwe_out);
-}
-
-}  // namespace
-
-extern "C" {
-
-int tfhe_mi355_context_create_u128(const TfheMi355Parameters *params, int device, TfheMi355Context **out_ctx) {
-    return guarded([&] {
-        if (!out_ctx) fail("null out_ctx");
-        *out_ctx = nullptr;
-        if (!params) fail("null params");
-        validate_shape128(*params);
-        *out_ctx = create_single(*params, device);
-        (*out_ctx)->for_u128 = true;
-    });
-}
-
-int tfhe_mi355_bootstrap_key_upload_u128(TfheMi355Context *ctx, const uint64_t *bsk, size_t len) {
-    return guarded([&] {
-        require_single128(ctx);
-        if (!bsk) fail("null argument");
-        KeyWrite kw(ctx);
-        require_width128(ctx);
-        validate_shape128(ctx->p);
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        if (len != ctx->std_bsk_len())
-            fail("bootstrapping key has %zu u128 words, expected %zu", len, ctx->std_bsk_len());
-        ctx->fbsk128_ready = false;
-        const size_t N = ctx->N(), M = N / 2;
-        std::vector<double> tab(4 * M + 4 * (M / 2));
-        fft128_host_tables((int)N, tab.data(), tab.data() + 4 * M);
-        ctx->tables128.reserve(tab.size() * sizeof(double));
-        check(hipMemcpyAsync(ctx->tables128.ptr, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice,
-                             ctx->stream),
-              "upload f128 tables");
-        ctx->std_staging.reserve(len * 16);
-        check(hipMemcpyAsync(ctx->std_staging.ptr, bsk, len * 16, hipMemcpyHostToDevice, ctx->stream),
-              "upload u128 bsk");
-        ctx->fbsk128.reserve(len / N * 4 * M * sizeof(double));
-        check(launch_bsk128_to_fourier((int)N, ctx->std_staging.ptr, (double *)ctx->fbsk128.ptr, len / N,
-                                       twist128(ctx), tw128(ctx), ctx->stream),
-              "u128 bsk conversion");
-        check(hipStreamSynchronize(ctx->stream), "u128 bsk conversion sync");
-        ctx->std_staging.release();
-        ctx->fbsk128_ready = true;
-    });
-}
-
-int tfhe_mi355_programmable_bootstrap_u128(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *lwe_out,
-                                           const uint64_t *luts, size_t lut_count, const uint32_t *lut_indexes,
-                                           size_t count, uint32_t ciphertext_modulus_log) {
-    return guarded(
-        [&] { pbs128_host(ctx, lwe_in, lwe_out, luts, lut_count, lut_indexes, count, ciphertext_modulus_log, false); });
-}
-
-int tfhe_mi355_blind_rotate_u128(TfheMi355Context *ctx, const uint64_t *lwe_in, uint64_t *glwe_out,
-                                 const uint64_t *luts, size_t lut_count, const uint32_t *lut_indexes, size_t count,
-                                 uint32_t ciphertext_modulus_log) {
-    return guarded(
-        [&] { pbs128_host(ctx, lwe_in, glwe_out, luts, lut_count, lut_indexes, count, ciphertext_modulus_log, true); });
-}
-
-int tfhe_mi355_programmable_bootstrap_u128_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes) {
-    return guarded([&] {
-        require_single128(ctx);
-        if (!bytes) fail("null argument");
-        *bytes = pbs128_scratch_bytes(ctx, count);
-    });
-}
-
-int tfhe_mi355_blind_rotate_u128_scratch(TfheMi355Context *ctx, size_t count, size_t *bytes) {
-    return tfhe_mi355_programmable_bootstrap_u128_scratch(ctx, count, bytes);
-}
-
-int tfhe_mi355_programmable_bootstrap_u128_async(TfheMi355Context *ctx, const uint64_t *d_in, uint64_t *d_out,
-                                                 const uint64_t *d_luts, size_t lut_count, const uint32_t *d_idx,
-                                                 size_t count, uint32_t ciphertext_modulus_log, void *d_scratch,
-                                                 size_t scratch_bytes, void *stream) {
-    return guarded([&] {
-        pbs128_async(ctx, d_in, d_out, d_luts, lut_count, d_idx, count, ciphertext_modulus_log, d_scratch,
-                     scratch_bytes, stream, false);
-    });
-}
-
-int tfhe_mi355_blind_rotate_u128_async(TfheMi355Context *ctx, const uint64_t *d_in, uint64_t *d_glwe_out,
-                                       const uint64_t *d_luts, size_t lut_count, const uint32_t *d_idx, size_t count,
-                                       uint32_t ciphertext_modulus_log, void *d_scratch, size_t scratch_bytes,
-                                       void *stream) {
-    return guarded([&] {
-        pbs128_async(ctx, d_in, d_glwe_out, d_luts, lut_count, d_idx, count, ciphertext_modulus_log, d_scratch,
-                     scratch_bytes, stream, true);
-    });
-}
-
-int tfhe_mi355_debug_fft128_tables(uint32_t polynomial_size, double *twist, double *twiddles) {
-    return guarded([&] {
-        if (!twist || !twiddles) fail("null argument");
-        const uint32_t N = polynomial_size;
-        if (N != 256 && N != 512 && N != 1024 && N != 2048)
-            fail("128-bit-torus PBS: polynomial_size must be 256, 512, 1024 or 2048 (got %u)", N);
-        fft128_host_tables((int)N, twist, twiddles);
-    });
-}
-
-int tfhe_mi355_debug_torus128_from_f128(int device, const double *hi, const double *lo, const uint64_t *acc,
-                                        uint64_t *out, size_t count) {
-    return guarded([&] {
-        if ((!hi || !lo || !out) && count) fail("null argument");
-        if (count == 0) return;
-        check(hipSetDevice(device), "hipSetDevice");
-        DeviceBuffer d_hi, d_lo, d_acc, d_out;
-        d_hi.reserve(count * sizeof(double));
-        d_lo.reserve(count * sizeof(double));
-        d_out.reserve(count * 16);
-        check(hipMemcpy(d_hi.ptr, hi, count * sizeof(double), hipMemcpyHostToDevice), "H2D hi");
-        check(hipMemcpy(d_lo.ptr, lo, count * sizeof(double), hipMemcpyHostToDevice), "H2D lo");
-        if (acc) {
-            d_acc.reserve(count * 16);
-            check(hipMemcpy(d_acc.ptr, acc, count * 16, hipMemcpyHostToDevice), "H2D acc");
-        }
-        check(launch_torus128_from_f128((const double *)d_hi.ptr, (const double *)d_lo.ptr, acc ? d_acc.ptr : nullptr,
-                                        d_out.ptr, count, nullptr),
-              "torus128 conversion");
-        check(hipMemcpy(out, d_out.ptr, count * 16, hipMemcpyDeviceToHost), "D2H out");
-    });
-}
-
-int tfhe_mi355_debug_pbs_u128_resident(TfheMi355Context *ctx, size_t *count) {
-    return guarded([&] {
-        require_single128(ctx);
-        if (!count) fail("null argument");
-        validate_shape128(ctx->p);
-        check(hipSetDevice(ctx->device), "hipSetDevice");
-        *count = (size_t)pbs_f128_resident_blocks((int)ctx->N(), (int)ctx->k());
     });
 }
 

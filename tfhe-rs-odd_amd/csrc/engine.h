@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-struct TfheMi355Context;  // include/tfhe_mi355.h (opaque there), capi.cpp
+struct TfheMi355Context;  // include/tfhe_mi355.h (opaque there), capi_internal.h
 
 namespace tfhe_mi355 {
 
