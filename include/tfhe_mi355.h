@@ -338,6 +338,84 @@ int tfhe_mi355_keyswitch_key_upload_seeded(TfheMi355Context *ctx, const uint64_t
 int tfhe_mi355_csprng_mask_words(TfheMi355Context *ctx, uint64_t seed_lo, uint64_t seed_hi, uint64_t *out,
                                  size_t words);
 
+/* ---- compressed ciphertext ingress --------------------------------------------------------------
+ * A client of the reference uploads ciphertexts in one of two compressed forms; the engine expands them
+ * on the GPU, so that only the compressed bytes cross PCIe.
+ *   shortint::CompactCiphertextList (shortint/ciphertext/mod.rs:521-594): an LweCompactCiphertextList
+ *     (entities/lwe_compact_ciphertext_list.rs) under a CompactPublicKey.  Container: [mask_count][n] masks,
+ *     then [count] bodies, mask_count = ceil(count / n).  Replaces CompactCiphertextList::expand
+ *     (expand_lwe_compact_ciphertext_list, lwe_compact_ciphertext_list_expansion.rs:12-58): row i takes the
+ *     mask of bin i / n multiplied by X^(n - (i % n + 1)) in Z[X]/(X^n + 1), and body i.  n is a power of two.
+ *   shortint::CompressedCiphertext (mod.rs:467-513): a SeededLweCiphertext<u64>, one body word and a 128-bit
+ *     CompressionSeed.  Replaces CompressedCiphertext::decompress (decompress_seeded_lwe_ciphertext,
+ *     seeded_lwe_ciphertext_decompression.rs:50-73) for a batch: row r's mask is words [0, n) of the AES-CTR
+ *     mask stream of ITS seed (see tfhe_mi355_csprng_mask_words); the key schedule runs on the device.
+ *   SeededLweCiphertextList (decompress_seeded_lwe_ciphertext_list, seeded_lwe_ciphertext_list_decompression.rs:
+ *     13-100): one seed for the list, row r's mask is words [r n, (r + 1) n) of its stream.
+ * Native 2^64 modulus only.  One descriptor names the source; the pointers inside are host pointers for the
+ * host-pointer calls and device pointers (16-byte aligned) for the _async calls, the descriptor itself is
+ * always host memory and is read before the call returns. */
+#define TFHE_MI355_LWE_SOURCE_ROWS 0         /* expanded rows */
+#define TFHE_MI355_LWE_SOURCE_COMPACT 1      /* compact list */
+#define TFHE_MI355_LWE_SOURCE_SEEDED_LIST 2  /* seeded list, one seed */
+#define TFHE_MI355_LWE_SOURCE_SEEDED_ROWS 3  /* seeded ciphertexts, a seed each */
+typedef struct {
+    uint32_t kind;          /* 0 expanded rows, 1 compact list, 2 seeded list (one seed), 3 seeded rows (a seed each) */
+    uint32_t lwe_dimension; /* n of the rows produced (row = n+1 words) */
+    const uint64_t *data;   /* 0: [count][n+1]; 1: the compact container; 2, 3: [count] bodies */
+    const uint64_t *seeds;  /* 2: {lo, hi}; 3: [count]{lo, hi}; otherwise NULL */
+} TfheMi355LweSource;
+
+/* Expansion alone: lwe_out = count rows of n + 1 words.  n is the caller's (it need not be the context's);
+ * any context of any width serves, on a multi-device context the first device.  count = 0 is a no-op.
+ * Refused (rc 1): an unknown kind, n = 0, kind 1 with n not a power of two, a missing pointer.  The _async
+ * form follows the header's rules (no allocation or synchronisation, scratch from the caller, nothing
+ * written outside rows [0, count) and [0, scratch_bytes), result independent of earlier contents); its
+ * scratch query is 0 for every kind but 2 (the AES tables of the list's seed). */
+int tfhe_mi355_lwe_expand(TfheMi355Context *ctx, const TfheMi355LweSource *src, size_t count, uint64_t *lwe_out);
+int tfhe_mi355_lwe_expand_scratch(TfheMi355Context *ctx, uint32_t kind, uint32_t lwe_dimension, size_t count,
+                                  size_t *bytes);
+int tfhe_mi355_lwe_expand_async(TfheMi355Context *ctx, const TfheMi355LweSource *d_src, size_t count,
+                                uint64_t *d_lwe_out, void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* Expansion composed with a keyed operation: op as in tfhe_mi355_submit (0 PBS, 1 KS -> PBS, 2 PBS -> KS,
+ * 3 KS); the outputs are, bit for bit, those of tfhe_mi355_lwe_expand followed by the operation's own entry
+ * point.  The host-pointer form sends the compressed source over PCIe once -- kind 1 whole, kinds 2 and 3 a
+ * slice of bodies (and seeds) per chunk of the host pipeline -- and expands each chunk on the device into the
+ * buffer the rows would have been copied to (chunks need not respect compact bins).  Kind 0 is the
+ * operation's existing call.  luts, lut_count and lut_indexes are ignored for op 3.
+ * Refused (rc 1, with a message): src->lwe_dimension other than the operation's input dimension on this
+ * context (n for ops 0 and 2, k N for ops 1 and 3); a multi-device context; a context holding 32-bit or
+ * 128-bit keys; a missing key.  These calls are not coalesced.  The _async form takes count * (input
+ * dimension + 1) words of its scratch for the expanded rows (tfhe_mi355_apply_from_scratch counts them in). */
+int tfhe_mi355_apply_from(TfheMi355Context *ctx, int op, const TfheMi355LweSource *src, uint64_t *lwe_out,
+                          const uint64_t *luts, size_t lut_count, const uint32_t *lut_indexes, size_t count);
+int tfhe_mi355_apply_from_scratch(TfheMi355Context *ctx, int op, uint32_t kind, size_t count, size_t *bytes);
+int tfhe_mi355_apply_from_async(TfheMi355Context *ctx, int op, const TfheMi355LweSource *d_src, uint64_t *d_lwe_out,
+                                const uint64_t *d_luts, size_t lut_count, const uint32_t *d_lut_indexes, size_t count,
+                                void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* The bincode bytes of the two shortint types, parsed without a GPU (field order: ct_list / ct, degree,
+ * message_modulus, carry_modulus, pbs_order, noise_level).  The u64 container stays where it is: a caller
+ * points TfheMi355LweSource.data at bytes + data_offset (bincode does not align it: copy the data_words words
+ * out if bytes + data_offset is not 8-byte aligned).  Truncated or inconsistent input fails with a message
+ * naming the field and byte offset; a non-native ciphertext modulus, or a compact container whose length is not
+ * lwe_compact_ciphertext_list_size(n, count) (lwe_compact_ciphertext_list.rs:55-63), is refused. */
+typedef struct {
+    uint32_t lwe_dimension;
+    uint32_t pbs_order;    /* PBSOrder: 0 KeyswitchBootstrap, 1 BootstrapKeyswitch */
+    uint64_t count;        /* ciphertexts (1 for a CompressedCiphertext) */
+    uint64_t degree;
+    uint64_t message_modulus;
+    uint64_t carry_modulus;
+    uint64_t noise_level;
+    uint64_t data_offset;  /* byte offset in `bytes` of the container (compact) or of the body word */
+    uint64_t data_words;   /* its length in u64 words */
+    uint64_t seed_lo, seed_hi; /* CompressedCiphertext: the CompressionSeed */
+} TfheMi355CiphertextInfo;
+int tfhe_mi355_compact_ciphertext_list_inspect(const uint8_t *bytes, size_t len, TfheMi355CiphertextInfo *info);
+int tfhe_mi355_compressed_ciphertext_inspect(const uint8_t *bytes, size_t len, TfheMi355CiphertextInfo *info);
+
 /* LWE -> GLWE packing keyswitch of the fork's tree bootstrapping (gadget ServerKey
  * lwe_packing_keyswitch_key, gadget/engine/bootstrapping.rs:345-352, used at :713,:744).
  * Key layout [k*N][level][(k+1)*N] (levels stored L..1), input key = the big LWE key.
@@ -817,6 +895,22 @@ int tfhe_mi355_client_gen_seeded_keyswitch_key(uint64_t noise_seed, uint64_t mas
                                                uint64_t *bodies);
 int tfhe_mi355_client_csprng_mask_words(uint64_t seed_lo, uint64_t seed_hi, uint64_t first_word, size_t count,
                                         uint64_t *out);
+/* compact public key [2n] = mask, body (generate_lwe_compact_public_key, lwe_compact_public_key_generation.rs:
+ * 15-54): body = mask (*) reverse(sk) + noise in Z[X]/(X^n + 1) */
+int tfhe_mi355_client_gen_compact_public_key(uint64_t seed, const uint64_t *sk, uint32_t n, double std_dev,
+                                             uint64_t *pk);
+/* compact list container, ceil(count / n) n + count words
+ * (encrypt_lwe_compact_ciphertext_list_with_compact_public_key, lwe_encryption.rs:1837-2043) */
+int tfhe_mi355_client_compact_encrypt(uint64_t seed, const uint64_t *pk, uint32_t n, const uint64_t *plaintexts,
+                                      size_t count, double mask_std_dev, double body_std_dev, uint64_t *list);
+/* seeded ciphertexts: the bodies under masks from the AES-CTR stream -- one seed each, seeds [count]{lo, hi}
+ * (encrypt_seeded_lwe_ciphertext, lwe_encryption.rs:1415-1585), or one seed for the list
+ * (encrypt_seeded_lwe_ciphertext_list, :1096-1253) */
+int tfhe_mi355_client_seeded_lwe_encrypt(uint64_t noise_seed, const uint64_t *seeds, const uint64_t *sk, uint32_t n,
+                                         const uint64_t *plaintexts, size_t count, double std_dev, uint64_t *bodies);
+int tfhe_mi355_client_seeded_lwe_encrypt_list(uint64_t noise_seed, uint64_t mask_seed_lo, uint64_t mask_seed_hi,
+                                              const uint64_t *sk, uint32_t n, const uint64_t *plaintexts, size_t count,
+                                              double std_dev, uint64_t *bodies);
 int tfhe_mi355_client_lwe_encrypt(uint64_t seed, const uint64_t *sk, uint32_t n, const uint64_t *plaintexts,
                                   size_t count, double std_dev, uint64_t *cts);
 int tfhe_mi355_client_lwe_decrypt(const uint64_t *sk, uint32_t n, const uint64_t *cts, size_t count,

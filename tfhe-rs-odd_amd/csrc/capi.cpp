@@ -1116,7 +1116,7 @@ void check_quad_fail(TfheMi355Context *c) {
 namespace tfhe_mi355::capi {
 void run_host_pipeline(TfheMi355Context *c, const uint64_t *in, size_t in_words, uint64_t *out, size_t out_words,
                        const uint64_t *luts, size_t lut_words, size_t lut_count, const uint32_t *idx, size_t count,
-                       ChunkLaunch launch, ScratchSize scratch_size) {
+                       ChunkLaunch launch, ScratchSize scratch_size, const ChunkSource *from) {
     if (count == 0) return;
     hipStream_t cs = c->stream;
     const uint64_t *d_luts = nullptr;
@@ -1127,7 +1127,7 @@ void run_host_pipeline(TfheMi355Context *c, const uint64_t *in, size_t in_words,
         d_luts = (const uint64_t *)c->io_luts.ptr;
     }
     // page-locked caller buffers are DMA'd directly (no staging copies on the host)
-    const bool pin_in = is_pinned(in, count * in_words * 8), pin_out = is_pinned(out, count * out_words * 8);
+    const bool pin_in = !from && is_pinned(in, count * in_words * 8), pin_out = is_pinned(out, count * out_words * 8);
     const size_t chunk = std::min(count, host_chunk(c, count));
     // kernels of consecutive chunks are ordered on cs: one scratch serves them all
     const size_t need_scratch = scratch_size ? scratch_size(c, chunk) : 0;
@@ -1138,16 +1138,20 @@ void run_host_pipeline(TfheMi355Context *c, const uint64_t *in, size_t in_words,
             TfheMi355Context::Lane &L = c->lanes[q];
             lane_finish(L, out, out_words);  // this lane's previous chunk: all its device work is done
             const size_t cnt = std::min(chunk, count - next);
-            if (!pin_in) L.h_in.reserve(chunk * in_words * 8);
+            if (!pin_in && !from) L.h_in.reserve(chunk * in_words * 8);
             if (!pin_out) L.h_out.reserve(chunk * out_words * 8);
             L.d_in.reserve(chunk * in_words * 8);
             L.d_out.reserve(chunk * out_words * 8);
-            const uint64_t *src = in + next * in_words;
-            if (!pin_in) {
-                std::memcpy(L.h_in.ptr, src, cnt * in_words * 8);
-                src = (const uint64_t *)L.h_in.ptr;
+            if (from) {  // the rows are written on the device from a compressed source
+                from->stage(L, next, cnt);
+            } else {
+                const uint64_t *src = in + next * in_words;
+                if (!pin_in) {
+                    std::memcpy(L.h_in.ptr, src, cnt * in_words * 8);
+                    src = (const uint64_t *)L.h_in.ptr;
+                }
+                check(hipMemcpyAsync(L.d_in.ptr, src, cnt * in_words * 8, hipMemcpyHostToDevice, L.stream), "H2D in");
             }
-            check(hipMemcpyAsync(L.d_in.ptr, src, cnt * in_words * 8, hipMemcpyHostToDevice, L.stream), "H2D in");
             const uint32_t *d_idx = nullptr;
             if (idx) {
                 L.h_idx.reserve(chunk * 4);
@@ -1158,6 +1162,7 @@ void run_host_pipeline(TfheMi355Context *c, const uint64_t *in, size_t in_words,
             }
             check(hipEventRecord(L.h2d, L.stream), "h2d event");
             check(hipStreamWaitEvent(cs, L.h2d, 0), "wait h2d");
+            if (from) from->expand(L, next, cnt, cs);
             launch(c, (const uint64_t *)L.d_in.ptr, (uint64_t *)L.d_out.ptr, d_luts, lut_count, d_idx, cnt,
                    need_scratch ? c->io_tmp.ptr : nullptr, need_scratch ? c->io_tmp.bytes : 0, cs);
             check(hipEventRecord(L.kern, cs), "kernel event");
@@ -1597,6 +1602,12 @@ TfheMi355Context *create_single(const TfheMi355Parameters &p, int device) {
             check(hipMemset(c->quad_fail.ptr, 0, 4), "quad fail word");
         }
         build_tables(c);
+        {  // AES tables for the ingress kernels (their Te0 and S-box; each call brings its own seeds)
+            std::vector<unsigned char> host(aes_tables_bytes());
+            aes_tables_build(0, 0, host.data());
+            c->aes_base.reserve(host.size());
+            check(hipMemcpy(c->aes_base.ptr, host.data(), host.size(), hipMemcpyHostToDevice), "upload aes tables");
+        }
     } catch (...) {
         tfhe_mi355_context_destroy(c);
         throw;

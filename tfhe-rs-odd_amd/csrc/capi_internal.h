@@ -1,8 +1,9 @@
 // capi_internal.h -- what the capi*.cpp files share: the host-side runtime behind include/tfhe_mi355.h is
 // split by subsystem (capi.cpp: contexts, keys, kernel-form policy, the u64 launchers and entry points with
 // the host-pointer pipeline, the request coalescer, the gadget layer and WoP-PBS; capi_multi.cpp: multi-device
-// contexts; capi_u32.cpp, capi_u128.cpp: the other torus widths).  What crosses a subsystem's boundary is
-// declared here, in namespace tfhe_mi355::capi; what one file alone uses stays in its anonymous namespace.
+// contexts; capi_u32.cpp, capi_u128.cpp: the other torus widths; capi_ingress.cpp: compressed ciphertext
+// sources).  What crosses a subsystem's boundary is declared here, in namespace tfhe_mi355::capi; what one file
+// alone uses stays in its anonymous namespace.
 // Included by those files only, never by a .hip file or by engine.h.
 #pragma once
 
@@ -225,6 +226,9 @@ struct TfheMi355Context {
     FftTables tables;
     DeviceBuffer fbsk, ksk, std_staging;
     DeviceBuffer io_luts, io_tmp;
+    // compressed ciphertext ingress (capi_ingress.cpp): what a host-pointer call sends up once (a compact
+    // container, the AES tables of a list's seed), and AES tables whose Te0 and S-box the kernels read
+    DeviceBuffer io_src, aes_base;
     DeviceBuffer ksk_planes;   // int8 byte planes of the KSK for the MFMA keyswitch
     // Host-pointer entry points: kernels run in chunk order on `stream`; each of two lanes has a
     // copy stream, page-locked staging and device in/out buffers, so that chunk i's copies (and
@@ -236,6 +240,7 @@ struct TfheMi355Context {
         hipEvent_t h2d = nullptr, kern = nullptr, done = nullptr;
         PinnedBuffer h_in, h_out, h_idx;
         DeviceBuffer d_in, d_out, d_idx;
+        DeviceBuffer d_src;  // a chunk's slice of a compressed source (capi_ingress.cpp)
         bool pending = false;
         bool direct_out = false;  // this chunk's D2H went straight into the caller's pinned buffer
         size_t first = 0, count = 0;
@@ -463,9 +468,16 @@ using ChunkLaunch = void (*)(TfheMi355Context *c, const uint64_t *d_in, uint64_t
                              size_t lut_count, const uint32_t *d_idx, size_t count, void *scratch,
                              size_t scratch_bytes, hipStream_t s);
 using ScratchSize = size_t (*)(const TfheMi355Context *c, size_t count);
+// a chunk's input rows written on the device instead of copied up: stage() enqueues what rows [first,
+// first + count) need on the lane's copy stream, expand() the kernels that fill L.d_in on the kernel stream
+// (after the lane's copies, before the chunk's launch)
+struct ChunkSource {
+    std::function<void(TfheMi355Context::Lane &L, size_t first, size_t count)> stage;
+    std::function<void(TfheMi355Context::Lane &L, size_t first, size_t count, hipStream_t s)> expand;
+};
 void run_host_pipeline(TfheMi355Context *c, const uint64_t *in, size_t in_words, uint64_t *out, size_t out_words,
                        const uint64_t *luts, size_t lut_words, size_t lut_count, const uint32_t *idx, size_t count,
-                       ChunkLaunch launch, ScratchSize scratch_size);
+                       ChunkLaunch launch, ScratchSize scratch_size, const ChunkSource *from = nullptr);
 void chunk_pbs(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *l, size_t lc, const uint32_t *x,
                size_t n, void *sc, size_t sb, hipStream_t s);
 void chunk_ks(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *, size_t, const uint32_t *,

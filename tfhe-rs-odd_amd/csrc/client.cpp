@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <cstring>
+#include <iterator>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -457,6 +458,82 @@ int tfhe_mi355_client_csprng_mask_words(uint64_t seed_lo, uint64_t seed_hi, uint
     return guard([&] {
         if (!out && count) throw std::invalid_argument("null argument");
         SeededMask(seed_lo, seed_hi).words(first_word, count, out);
+    });
+}
+
+// Compact public key [2n] = mask, body (generate_lwe_compact_public_key, lwe_compact_public_key_generation.rs:
+// 15-54): a uniform mask a, body = a (*) reverse(s) + e in Z[X]/(X^n + 1)
+// (slice_semi_reverse_negacyclic_convolution, slice_algorithms.rs:621-659).
+int tfhe_mi355_client_gen_compact_public_key(uint64_t seed, const uint64_t *sk, uint32_t n, double std, uint64_t *pk) {
+    return guard([&] {
+        if (!sk || !pk) throw std::invalid_argument("null argument");
+        if (n == 0 || (n & (n - 1))) throw std::invalid_argument("compact public key: lwe_dimension must be a power of two");
+        Rng r(seed, 0xA000000ULL);
+        for (uint32_t i = 0; i < n; i++) pk[i] = r.next();
+        const std::vector<uint64_t> rev(std::make_reverse_iterator(sk + n), std::make_reverse_iterator(sk));
+        std::fill(pk + n, pk + 2 * (size_t)n, 0);
+        negacyclic_binary_add(pk + n, pk, rev.data(), (int)n);
+        for (uint32_t i = 0; i < n; i++) pk[n + i] += r.gaussian_torus(std);
+    });
+}
+
+// Compact list container [ceil(count / n)][n] masks then [count] bodies
+// (encrypt_lwe_compact_ciphertext_list_with_compact_public_key, lwe_encryption.rs:1837-1955): per bin of n
+// ciphertexts a binary vector r; mask = pk_mask (*) reverse(r) + e1, body_i = (pk_body (*) reverse(r))_i + e2_i
+// + plaintext_i.  Every bin draws from its own stream.
+int tfhe_mi355_client_compact_encrypt(uint64_t seed, const uint64_t *pk, uint32_t n, const uint64_t *pts, size_t count,
+                                      double mask_std, double body_std, uint64_t *list) {
+    return guard([&] {
+        if (!pk || (!pts && count) || (!list && count)) throw std::invalid_argument("null argument");
+        if (n == 0 || (n & (n - 1))) throw std::invalid_argument("compact encryption: lwe_dimension must be a power of two");
+        const size_t bins = (count + n - 1) / n;
+        uint64_t *bodies = list + bins * n;
+        std::vector<uint64_t> rev(n), conv(n);
+        for (size_t b = 0; b < bins; b++) {
+            Rng r(seed, 0xB000000ULL + b);
+            for (uint32_t i = 0; i < n; i++) rev[n - 1 - i] = r.next() >> 63;
+            uint64_t *mask = list + b * n;
+            std::fill(mask, mask + n, 0);
+            negacyclic_binary_add(mask, pk, rev.data(), (int)n);
+            std::fill(conv.begin(), conv.end(), 0);
+            negacyclic_binary_add(conv.data(), pk + n, rev.data(), (int)n);
+            for (uint32_t i = 0; i < n; i++) mask[i] += r.gaussian_torus(mask_std);
+            const size_t in_bin = std::min<size_t>(n, count - b * n);
+            for (size_t i = 0; i < in_bin; i++) bodies[b * n + i] = conv[i] + r.gaussian_torus(body_std) + pts[b * n + i];
+        }
+    });
+}
+
+// Seeded ciphertexts, one CompressionSeed each (encrypt_seeded_lwe_ciphertext, lwe_encryption.rs:1415-1585): the
+// mask is words [0, n) of the seed's AES-CTR stream, only the body is kept.  seeds: [count]{lo, hi}.
+int tfhe_mi355_client_seeded_lwe_encrypt(uint64_t noise_seed, const uint64_t *seeds, const uint64_t *sk, uint32_t n,
+                                         const uint64_t *pts, size_t count, double std, uint64_t *bodies) {
+    return guard([&] {
+        if (!sk || (count && (!seeds || !pts || !bodies))) throw std::invalid_argument("null argument");
+        Rng r(noise_seed, 0xC000000ULL);
+        std::vector<uint64_t> ct((size_t)n + 1);
+        for (size_t c = 0; c < count; c++) {
+            const SeededMask mask(seeds[2 * c], seeds[2 * c + 1]);
+            lwe_encrypt(r, sk, (int)n, pts[c], std, ct.data(), &mask, 0);
+            bodies[c] = ct[n];
+        }
+    });
+}
+
+// A seeded list under one seed (encrypt_seeded_lwe_ciphertext_list, lwe_encryption.rs:1096-1253): ciphertext c
+// takes mask words [c n, (c + 1) n) of the stream.
+int tfhe_mi355_client_seeded_lwe_encrypt_list(uint64_t noise_seed, uint64_t mask_seed_lo, uint64_t mask_seed_hi,
+                                              const uint64_t *sk, uint32_t n, const uint64_t *pts, size_t count,
+                                              double std, uint64_t *bodies) {
+    return guard([&] {
+        if (!sk || (count && (!pts || !bodies))) throw std::invalid_argument("null argument");
+        const SeededMask mask(mask_seed_lo, mask_seed_hi);
+        Rng r(noise_seed, 0xD000000ULL);
+        std::vector<uint64_t> ct((size_t)n + 1);
+        for (size_t c = 0; c < count; c++) {
+            lwe_encrypt(r, sk, (int)n, pts[c], std, ct.data(), &mask, (uint64_t)c * n);
+            bodies[c] = ct[n];
+        }
     });
 }
 

@@ -14,53 +14,18 @@
 //
 // AES-128: T-table form (Te0 and the S-box in LDS, Te1..Te3 as byte rotations of Te0), round
 // keys expanded once on the host.  Checked bit-exact against the oracle's FIPS-197 restatement.
+#include "aes_device.h"
 #include "engine.h"
 
 namespace tfhe_mi355 {
 
-namespace {
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int s) { return (x << s) | (x >> (32 - s)); }
-}  // namespace
-
-// columns packed little-endian: word c = s[4c] | s[4c+1] << 8 | s[4c+2] << 16 | s[4c+3] << 24
-__device__ __forceinline__ void aes128_encrypt_block(const uint32_t *__restrict__ rk, const uint32_t *te,
-                                                     const uint8_t *sb, uint32_t s[4]) {
-#pragma unroll
-    for (int c = 0; c < 4; c++) s[c] ^= rk[c];
-#pragma unroll
-    for (int round = 1; round < 10; round++) {
-        uint32_t t[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            t[c] = te[s[c] & 0xff] ^ rotl32(te[(s[(c + 1) & 3] >> 8) & 0xff], 8) ^
-                   rotl32(te[(s[(c + 2) & 3] >> 16) & 0xff], 16) ^ rotl32(te[s[(c + 3) & 3] >> 24], 24) ^
-                   rk[4 * round + c];
-        }
-#pragma unroll
-        for (int c = 0; c < 4; c++) s[c] = t[c];
-    }
-    uint32_t t[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        t[c] = ((uint32_t)sb[s[c] & 0xff] | ((uint32_t)sb[(s[(c + 1) & 3] >> 8) & 0xff] << 8) |
-                ((uint32_t)sb[(s[(c + 2) & 3] >> 16) & 0xff] << 16) | ((uint32_t)sb[s[(c + 3) & 3] >> 24] << 24)) ^
-               rk[40 + c];
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) s[c] = t[c];
-}
-
-struct AesTables {
-    uint32_t rk[44];
-    uint32_t te0[256];
-    uint8_t sbox[256];
-};
-
-// Mask words [0, words) of the key, written into rows: word w -> out[(w / row_words) * stride +
-// w % row_words].  Thread a encrypts counter a: its bytes 1..8 are word 2a, bytes 9..15 the low 7
+// Mask words [first, first + words) of the stream, written into rows: word w -> out[(r / row_words) * stride +
+// r % row_words] with r = w - first (a key starts at first = 0; a chunk of a seeded ciphertext list starts at
+// its first row's word).  Thread a encrypts counter a: its bytes 1..8 are word 2a, bytes 9..15 the low 7
 // bytes of word 2a+1, byte 0 the top byte of word 2a-1.
-__global__ void __launch_bounds__(256) csprng_mask_kernel(const AesTables *__restrict__ tab, size_t words,
-                                                          size_t row_words, size_t stride, uint8_t *__restrict__ out) {
+__global__ void __launch_bounds__(256) csprng_mask_kernel(const AesTables *__restrict__ tab, size_t first,
+                                                          size_t words, size_t row_words, size_t stride,
+                                                          uint8_t *__restrict__ out) {
     __shared__ uint32_t te[256];
     __shared__ uint8_t sb[256];
     __shared__ uint32_t rk[44];
@@ -68,23 +33,29 @@ __global__ void __launch_bounds__(256) csprng_mask_kernel(const AesTables *__res
     sb[threadIdx.x] = tab->sbox[threadIdx.x];
     if (threadIdx.x < 44) rk[threadIdx.x] = tab->rk[threadIdx.x];
     __syncthreads();
-    const size_t blocks = (words + 1) / 2 + 1;  // counters touching words [0, words)
-    for (size_t a = (size_t)blockIdx.x * 256 + threadIdx.x; a < blocks; a += (size_t)gridDim.x * 256) {
+    const size_t end = first + words;
+    const size_t a0 = first / 2, blocks = (end + 1) / 2 - a0 + 1;  // counters touching words [first, end)
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < blocks; i += (size_t)gridDim.x * 256) {
+        const size_t a = a0 + i;
         uint32_t s[4] = {(uint32_t)a, (uint32_t)((uint64_t)a >> 32), 0u, 0u};  // u128 counter, LE
         aes128_encrypt_block(rk, te, sb, s);
-        auto word_addr = [&](size_t w) { return out + ((w / row_words) * stride + w % row_words) * 8; };
+        auto inside = [&](size_t w) { return w >= first && w < end; };
+        auto word_addr = [&](size_t w) {
+            const size_t r = w - first;
+            return out + ((r / row_words) * stride + r % row_words) * 8;
+        };
         const size_t w0 = 2 * a;
-        if (w0 < words) {  // bytes 1..8 -> word 2a
+        if (inside(w0)) {  // bytes 1..8 -> word 2a
             const uint64_t lo = (uint64_t)s[0] | ((uint64_t)s[1] << 32), hi = (uint64_t)s[2] | ((uint64_t)s[3] << 32);
             *reinterpret_cast<uint64_t *>(word_addr(w0)) = (lo >> 8) | (hi << 56);
         }
-        if (w0 + 1 < words) {  // bytes 9..15 -> bytes 0..6 of word 2a+1
+        if (inside(w0 + 1)) {  // bytes 9..15 -> bytes 0..6 of word 2a+1
             uint8_t *p = word_addr(w0 + 1);
             const uint64_t hi = (uint64_t)s[2] | ((uint64_t)s[3] << 32);
 #pragma unroll
             for (int b = 0; b < 7; b++) p[b] = (uint8_t)(hi >> (8 * (b + 1)));
         }
-        if (a >= 1 && w0 - 1 < words) word_addr(w0 - 1)[7] = (uint8_t)s[0];  // byte 0 -> top of word 2a-1
+        if (a >= 1 && inside(w0 - 1)) word_addr(w0 - 1)[7] = (uint8_t)s[0];  // byte 0 -> top of word 2a-1
     }
 }
 
@@ -98,16 +69,19 @@ __global__ void __launch_bounds__(256) seeded_body_kernel(const uint64_t *__rest
     out[r * stride + row_words + j] = bodies[e];
 }
 
-hipError_t launch_seeded_decompress(const void *d_tables, const uint64_t *d_bodies, size_t rows, size_t row_words,
-                                    size_t body_words, uint64_t *d_out, hipStream_t s) {
+// rows [first_row, first_row + rows) of the seeded entity whose masks are one stream; d_bodies and d_out are
+// those rows' (a whole key: first_row = 0)
+hipError_t launch_seeded_decompress_from(const void *d_tables, const uint64_t *d_bodies, size_t first_row, size_t rows,
+                                         size_t row_words, size_t body_words, uint64_t *d_out, hipStream_t s) {
     if (rows == 0) return hipSuccess;
     const size_t stride = row_words + body_words;
     const size_t words = rows * row_words;
     if (words) {
-        const size_t blocks = (words + 1) / 2 + 1;
+        const size_t first = first_row * row_words;
+        const size_t blocks = (first + words + 1) / 2 - first / 2 + 1;
         const unsigned grid = (unsigned)std::min<size_t>((blocks + 255) / 256, 65536);
         hipLaunchKernelGGL(csprng_mask_kernel, dim3(grid), dim3(256), 0, s,
-                           reinterpret_cast<const AesTables *>(d_tables), words, row_words, stride,
+                           reinterpret_cast<const AesTables *>(d_tables), first, words, row_words, stride,
                            reinterpret_cast<uint8_t *>(d_out));
     }
     const size_t n = rows * body_words;
@@ -115,6 +89,11 @@ hipError_t launch_seeded_decompress(const void *d_tables, const uint64_t *d_bodi
         hipLaunchKernelGGL(seeded_body_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_bodies, rows,
                            body_words, row_words, stride, d_out);
     return hipGetLastError();
+}
+
+hipError_t launch_seeded_decompress(const void *d_tables, const uint64_t *d_bodies, size_t rows, size_t row_words,
+                                    size_t body_words, uint64_t *d_out, hipStream_t s) {
+    return launch_seeded_decompress_from(d_tables, d_bodies, 0, rows, row_words, body_words, d_out, s);
 }
 
 // host copy of the block function (client-side seeded keygen uses the same tables)

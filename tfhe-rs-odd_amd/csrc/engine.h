@@ -446,5 +446,20 @@ void aes_tables_build(uint64_t seed_lo, uint64_t seed_hi, void *host_tables);
 void aes128_encrypt_host(const void *host_tables, uint32_t s[4]);
 hipError_t launch_seeded_decompress(const void *d_tables, const uint64_t *d_bodies, size_t rows, size_t row_words,
                                     size_t body_words, uint64_t *d_out, hipStream_t s);
+// the same for rows [first_row, first_row + rows) of the entity (d_bodies and d_out are those rows')
+hipError_t launch_seeded_decompress_from(const void *d_tables, const uint64_t *d_bodies, size_t first_row, size_t rows,
+                                         size_t row_words, size_t body_words, uint64_t *d_out, hipStream_t s);
+
+// compressed ciphertext ingress (lwe_ingress.hip): LWE rows of n + 1 words written from a compact list or
+// from seeded ciphertexts.  d_base_tables: AES tables of any seed (their Te0 and S-box are read).
+// rows [first, first + count) of the compact list whose bin masks are d_masks[bin][n]; d_bodies and d_out
+// are those rows'
+hipError_t launch_lwe_compact_expand(const uint64_t *d_masks, const uint64_t *d_bodies, size_t n, size_t first,
+                                     size_t count, uint64_t *d_out, hipStream_t s);
+// the tables of the seed {lo, hi} at d_seed, written to d_tables (aes_tables_bytes())
+hipError_t launch_aes_schedule(const void *d_base_tables, const uint64_t *d_seed, void *d_tables, hipStream_t s);
+// row r: mask = stream bytes [1, 1 + 8n) of the seed d_seeds[2r], d_seeds[2r + 1]; body = d_bodies[r]
+hipError_t launch_csprng_rows(const void *d_base_tables, const uint64_t *d_seeds, const uint64_t *d_bodies, size_t n,
+                              size_t count, uint64_t *d_out, hipStream_t s);
 
 }  // namespace tfhe_mi355

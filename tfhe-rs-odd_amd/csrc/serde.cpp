@@ -93,8 +93,10 @@ void abi(int rc) {
 struct Reader {
     const uint8_t *p;
     size_t n, off = 0;
+    const char *entity = "key";  // what the bytes hold, for the messages
     void need(size_t b, const char *what) const {
-        if (n - off < b) fail("serialized key truncated: %s at byte %zu needs %zu bytes, %zu left", what, off, b, n - off);
+        if (n - off < b)
+            fail("serialized %s truncated: %s at byte %zu needs %zu bytes, %zu left", entity, what, off, b, n - off);
     }
     uint8_t u8(const char *what) {
         need(1, what);
@@ -126,7 +128,8 @@ struct Reader {
     // Vec<u64>: length, then the words (left in place; possibly unaligned)
     size_t vec_u64(const char *what, size_t &count) {
         count = u64(what);
-        if (count > (n - off) / 8) fail("serialized key truncated: %s declares %zu words, %zu bytes left", what, count, n - off);
+        if (count > (n - off) / 8)
+            fail("serialized %s truncated: %s declares %zu words, %zu bytes left", entity, what, count, n - off);
         const size_t at = off;
         off += count * 8;
         return at;
@@ -353,7 +356,74 @@ void require_same(const TfheMi355Parameters &key, const TfheMi355Parameters &ctx
 #undef SAME
 }
 
+// ---- ciphertexts (compressed ingress) ---------------------------------------------------------------
+//   CompactCiphertextList (shortint/ciphertext/mod.rs:521-529)
+//     ct_list: LweCompactCiphertextList<Vec<u64>> (entities/lwe_compact_ciphertext_list.rs:19-27):
+//         data Vec<u64> [mask_count][n] masks then [count] bodies, lwe_size, lwe_ciphertext_count,
+//         ciphertext_modulus
+//     degree, message_modulus, carry_modulus: usize; pbs_order: PBSOrder (u32); noise_level: usize
+//   CompressedCiphertext (mod.rs:467-476)
+//     ct: SeededLweCiphertext<u64> (entities/seeded_lwe_ciphertext.rs:13-18): data u64 (the body), lwe_size,
+//         compression_seed, ciphertext_modulus
+//     degree, message_modulus, carry_modulus, pbs_order, noise_level
+void ciphertext_tail(Reader &r, TfheMi355CiphertextInfo *info) {
+    info->degree = r.u64("degree");
+    info->message_modulus = r.u64("message_modulus");
+    info->carry_modulus = r.u64("carry_modulus");
+    info->pbs_order = r.u32("pbs_order");
+    if (info->pbs_order > 1) fail("pbs_order variant %u at byte %zu", info->pbs_order, r.off - 4);
+    info->noise_level = r.u64("noise_level");
+    if (r.off != r.n) fail("%zu trailing bytes after the %s", r.n - r.off, r.entity);
+}
+
+uint32_t lwe_dimension_of(uint64_t lwe_size, size_t at) {
+    if (lwe_size < 2 || lwe_size > kMaxLweSize) fail("lwe_size = %llu at byte %zu out of range [2, %llu]",
+                                                     (unsigned long long)lwe_size, at, (unsigned long long)kMaxLweSize);
+    return (uint32_t)(lwe_size - 1);
+}
+
 }  // namespace
+
+int tfhe_mi355_compact_ciphertext_list_inspect(const uint8_t *bytes, size_t len, TfheMi355CiphertextInfo *info) {
+    return guarded([&] {
+        if (!bytes || !info) fail("null argument");
+        std::memset(info, 0, sizeof *info);
+        Reader r{bytes, len};
+        r.entity = "compact ciphertext list";
+        size_t words = 0;
+        info->data_offset = r.vec_u64("compact list data", words);
+        info->data_words = words;
+        const uint64_t lwe_size = r.u64("lwe_size");
+        const uint64_t n = info->lwe_dimension = lwe_dimension_of(lwe_size, r.off - 8);
+        info->count = r.u64("lwe_ciphertext_count");
+        ciphertext_modulus(r, "compact ciphertext list");
+        if (n & (n - 1)) fail("compact ciphertext list: lwe_dimension %llu is not a power of two", (unsigned long long)n);
+        // lwe_compact_ciphertext_list_size: one mask per bin of n ciphertexts, then the bodies
+        if (info->count > words || (info->count + n - 1) / n * n + info->count != words)
+            fail("compact ciphertext list: %zu data words for %llu ciphertexts of dimension %llu, expected %llu", words,
+                 (unsigned long long)info->count, (unsigned long long)n,
+                 (unsigned long long)((info->count + n - 1) / n * n + info->count));
+        ciphertext_tail(r, info);
+    });
+}
+
+int tfhe_mi355_compressed_ciphertext_inspect(const uint8_t *bytes, size_t len, TfheMi355CiphertextInfo *info) {
+    return guarded([&] {
+        if (!bytes || !info) fail("null argument");
+        std::memset(info, 0, sizeof *info);
+        Reader r{bytes, len};
+        r.entity = "compressed ciphertext";
+        info->data_offset = r.off;
+        (void)r.u64("seeded ciphertext body");
+        info->data_words = 1;
+        info->count = 1;
+        const uint64_t lwe_size = r.u64("lwe_size");
+        info->lwe_dimension = lwe_dimension_of(lwe_size, r.off - 8);
+        r.u128("compression_seed", info->seed_lo, info->seed_hi);
+        ciphertext_modulus(r, "compressed ciphertext");
+        ciphertext_tail(r, info);
+    });
+}
 
 // engine Fourier layout: element e of a polynomial -> natural frequency index
 int tfhe_mi355_fourier_engine_frequency(uint32_t N, uint32_t *freq) {

@@ -5,6 +5,6 @@ No CPU fallback: every compute call goes through the HIP engine.
 """
 from . import boolean, parameters
 from ._lib import EngineError, LIB_PATH, load
-from .engine import Engine, device_count, fill_accumulator, pinned_empty
+from .engine import Engine, LweSource, device_count, fill_accumulator, pinned_empty
 
-__all__ = ["parameters", "boolean", "Engine", "EngineError", "LIB_PATH", "load", "device_count", "fill_accumulator"]
+__all__ = ["parameters", "boolean", "Engine", "LweSource", "EngineError", "LIB_PATH", "load", "device_count", "fill_accumulator"]

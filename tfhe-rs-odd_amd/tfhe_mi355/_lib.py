@@ -47,6 +47,33 @@ class TfheMi355ServerKeyInfo(ctypes.Structure):
     ]
 
 
+class TfheMi355LweSource(ctypes.Structure):
+    """kind: 0 expanded rows, 1 compact list, 2 seeded list (one seed), 3 seeded rows (a seed each); data and
+    seeds are host pointers for the host-pointer calls, device pointers for the _async calls."""
+    _fields_ = [
+        ("kind", ctypes.c_uint32),
+        ("lwe_dimension", ctypes.c_uint32),
+        ("data", ctypes.c_void_p),
+        ("seeds", ctypes.c_void_p),
+    ]
+
+
+class TfheMi355CiphertextInfo(ctypes.Structure):
+    _fields_ = [
+        ("lwe_dimension", ctypes.c_uint32),
+        ("pbs_order", ctypes.c_uint32),
+        ("count", ctypes.c_uint64),
+        ("degree", ctypes.c_uint64),
+        ("message_modulus", ctypes.c_uint64),
+        ("carry_modulus", ctypes.c_uint64),
+        ("noise_level", ctypes.c_uint64),
+        ("data_offset", ctypes.c_uint64),
+        ("data_words", ctypes.c_uint64),
+        ("seed_lo", ctypes.c_uint64),
+        ("seed_hi", ctypes.c_uint64),
+    ]
+
+
 u8p = ctypes.POINTER(ctypes.c_uint8)
 
 # (name, restype, argtypes) -- every symbol declared in include/tfhe_mi355.h
@@ -167,6 +194,25 @@ SIGNATURES = [
     ("tfhe_mi355_bootstrap_key_upload_seeded", ctypes.c_int, [vp, u64p, sz, ctypes.c_uint64, ctypes.c_uint64]),
     ("tfhe_mi355_keyswitch_key_upload_seeded", ctypes.c_int, [vp, u64p, sz, ctypes.c_uint64, ctypes.c_uint64]),
     ("tfhe_mi355_csprng_mask_words", ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, u64p, sz]),
+    # compressed ciphertext ingress
+    ("tfhe_mi355_lwe_expand", ctypes.c_int, [vp, ctypes.POINTER(TfheMi355LweSource), sz, u64p]),
+    ("tfhe_mi355_lwe_expand_scratch", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_lwe_expand_async", ctypes.c_int, [vp, ctypes.POINTER(TfheMi355LweSource), sz, vp, vp, sz, vp]),
+    ("tfhe_mi355_apply_from", ctypes.c_int,
+     [vp, ctypes.c_int, ctypes.POINTER(TfheMi355LweSource), u64p, u64p, sz, u32p, sz]),
+    ("tfhe_mi355_apply_from_scratch", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_uint32, sz, ctypes.POINTER(sz)]),
+    ("tfhe_mi355_apply_from_async", ctypes.c_int,
+     [vp, ctypes.c_int, ctypes.POINTER(TfheMi355LweSource), vp, vp, sz, vp, sz, vp, sz, vp]),
+    ("tfhe_mi355_compact_ciphertext_list_inspect", ctypes.c_int, [u8p, sz, ctypes.POINTER(TfheMi355CiphertextInfo)]),
+    ("tfhe_mi355_compressed_ciphertext_inspect", ctypes.c_int, [u8p, sz, ctypes.POINTER(TfheMi355CiphertextInfo)]),
+    ("tfhe_mi355_client_gen_compact_public_key", ctypes.c_int,
+     [ctypes.c_uint64, u64p, ctypes.c_uint32, ctypes.c_double, u64p]),
+    ("tfhe_mi355_client_compact_encrypt", ctypes.c_int,
+     [ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, sz, ctypes.c_double, ctypes.c_double, u64p]),
+    ("tfhe_mi355_client_seeded_lwe_encrypt", ctypes.c_int,
+     [ctypes.c_uint64, u64p, u64p, ctypes.c_uint32, u64p, sz, ctypes.c_double, u64p]),
+    ("tfhe_mi355_client_seeded_lwe_encrypt_list", ctypes.c_int,
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, sz, ctypes.c_double, u64p]),
     ("tfhe_mi355_debug_torus_from_fraction", ctypes.c_int,
      [ctypes.c_int, ctypes.POINTER(ctypes.c_double), u64p, u64p, sz]),
     ("tfhe_mi355_client_gen_seeded_bootstrap_key", ctypes.c_int,

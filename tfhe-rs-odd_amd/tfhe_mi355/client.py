@@ -165,6 +165,65 @@ def lwe_decrypt(sk, cts) -> np.ndarray:
     return pts
 
 
+# ---- compressed ciphertext forms (compact public key, seeded ciphertexts) ----------------------------
+def _seed_words(seeds) -> np.ndarray:
+    """[count][2] = {lo, hi} words of 128-bit seeds given as Python ints"""
+    return np.array([[int(s) & 0xFFFFFFFFFFFFFFFF, (int(s) >> 64) & 0xFFFFFFFFFFFFFFFF] for s in seeds],
+                    dtype=np.uint64).reshape(-1, 2)
+
+
+def gen_compact_public_key(seed, sk, std_dev) -> np.ndarray:
+    """[2n] = mask, body (generate_lwe_compact_public_key, lwe_compact_public_key_generation.rs:15-54); n a
+    power of two."""
+    sk = np.ascontiguousarray(sk, dtype=np.uint64)
+    pk = np.empty(2 * len(sk), dtype=np.uint64)
+    _lib.call("tfhe_mi355_client_gen_compact_public_key", seed, _ptr(sk), len(sk), std_dev, _ptr(pk))
+    return pk
+
+
+def compact_list_words(lwe_dimension: int, count: int) -> int:
+    """lwe_compact_ciphertext_list_size (entities/lwe_compact_ciphertext_list.rs:55-63)"""
+    return -(-count // lwe_dimension) * lwe_dimension + count
+
+
+def compact_encrypt(seed, pk, plaintexts, mask_std_dev, body_std_dev=None) -> np.ndarray:
+    """The container of an LweCompactCiphertextList, [ceil(count / n)][n] masks then [count] bodies
+    (encrypt_lwe_compact_ciphertext_list_with_compact_public_key, lwe_encryption.rs:1837-2043)."""
+    pk = np.ascontiguousarray(pk, dtype=np.uint64)
+    n = len(pk) // 2
+    pts = np.ascontiguousarray(plaintexts, dtype=np.uint64).ravel()
+    out = np.empty(compact_list_words(n, len(pts)), dtype=np.uint64)
+    _lib.call("tfhe_mi355_client_compact_encrypt", seed, _ptr(pk), n, _ptr(pts), len(pts), mask_std_dev,
+              mask_std_dev if body_std_dev is None else body_std_dev, _ptr(out))
+    return out
+
+
+def seeded_lwe_encrypt(noise_seed, seeds, sk, plaintexts, std_dev) -> np.ndarray:
+    """Bodies of seeded ciphertexts, one 128-bit CompressionSeed each (encrypt_seeded_lwe_ciphertext,
+    lwe_encryption.rs:1415-1585): the mask of ciphertext c is words [0, n) of the stream of seeds[c]."""
+    sk = np.ascontiguousarray(sk, dtype=np.uint64)
+    pts = np.ascontiguousarray(plaintexts, dtype=np.uint64).ravel()
+    sw = _seed_words(seeds)
+    if len(sw) != len(pts):
+        raise ValueError("one seed per plaintext")
+    bodies = np.empty(len(pts), dtype=np.uint64)
+    _lib.call("tfhe_mi355_client_seeded_lwe_encrypt", noise_seed, _ptr(sw), _ptr(sk), len(sk), _ptr(pts), len(pts),
+              std_dev, _ptr(bodies))
+    return bodies
+
+
+def seeded_lwe_encrypt_list(noise_seed, compression_seed: int, sk, plaintexts, std_dev) -> np.ndarray:
+    """Bodies of a seeded list under one seed (encrypt_seeded_lwe_ciphertext_list, lwe_encryption.rs:1096-1253):
+    ciphertext c takes mask words [c n, (c + 1) n) of the stream."""
+    sk = np.ascontiguousarray(sk, dtype=np.uint64)
+    pts = np.ascontiguousarray(plaintexts, dtype=np.uint64).ravel()
+    bodies = np.empty(len(pts), dtype=np.uint64)
+    _lib.call("tfhe_mi355_client_seeded_lwe_encrypt_list", noise_seed, compression_seed & 0xFFFFFFFFFFFFFFFF,
+              (compression_seed >> 64) & 0xFFFFFFFFFFFFFFFF, _ptr(sk), len(sk), _ptr(pts), len(pts), std_dev,
+              _ptr(bodies))
+    return bodies
+
+
 def decode(plaintexts, delta: int) -> np.ndarray:
     """shortint decrypt_message_and_carry rounding (shortint/client_key/mod.rs:281-302)."""
     d = np.asarray(plaintexts, dtype=np.uint64)

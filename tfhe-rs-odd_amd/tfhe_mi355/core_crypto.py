@@ -17,6 +17,10 @@
                                                   lwe_bootstrap_key_conversion.rs:164
   programmable_bootstrap_f128_lwe_ciphertext      lwe_programmable_bootstrapping.rs:1378-1459
 
+  expand_lwe_compact_ciphertext_list              lwe_compact_ciphertext_list_expansion.rs:12-58 (par_: 61-107)
+  decompress_seeded_lwe_ciphertext_list           seeded_lwe_ciphertext_list_decompression.rs:13-100
+  decompress_seeded_lwe_ciphertext                seeded_lwe_ciphertext_decompression.rs:50-73
+
 Argument meaning and error behaviour follow the reference: output buffers are caller-owned and
 overwritten; dimension mismatches raise (the reference asserts, lwe_programmable_bootstrapping.rs
 :1088-1102, lwe_keyswitch.rs:106-141).  The `_batch` forms are the engine's native shape.
@@ -25,7 +29,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import Engine
+from .engine import Engine, LweSource
 from .parameters import ClassicPBSParameters
 
 
@@ -370,3 +374,39 @@ def circuit_bootstrap_boolean_vertical_packing(big_lut_as_polynomial_list: np.nd
         raise ValueError(f"{npolys} LUT polynomials do not divide into {nout} outputs")
     lut = big_lut_as_polynomial_list.reshape(1, nout, npolys // nout, N)
     lwe_list_out[...] = eng.circuit_bootstrap_vertical_packing(lwe_list_in[None], base_log_cbs, level_cbs, lut)[0]
+
+
+# ---- compressed ciphertext ingress ----------------------------------------------------------------------
+def _check_rows(output: np.ndarray, count: int, n: int) -> None:
+    if output.size != count * (n + 1) or output.shape[-1] != n + 1:
+        raise ValueError(f"Mismatched output list: {output.shape} for {count} ciphertexts of LweSize {n + 1}")
+
+
+def expand_lwe_compact_ciphertext_list(output_lwe_ciphertext_list: np.ndarray, input_container: np.ndarray,
+                                       engine: Engine) -> None:
+    """output [count][n+1] <- the compact container [ceil(count / n)][n] masks then [count] bodies; the reference
+    asserts the same count and LweSize on both sides."""
+    out = output_lwe_ciphertext_list
+    n = out.shape[-1] - 1
+    count = out.size // (n + 1)
+    src = LweSource("compact", n, input_container, count=count)
+    out[...] = engine.lwe_expand(src).reshape(out.shape)
+
+
+par_expand_lwe_compact_ciphertext_list = expand_lwe_compact_ciphertext_list
+
+
+def decompress_seeded_lwe_ciphertext_list(output_list: np.ndarray, bodies: np.ndarray, compression_seed: int,
+                                          engine: Engine) -> None:
+    """output [count][n+1] <- a SeededLweCiphertextList (bodies and one CompressionSeed)"""
+    b = np.ascontiguousarray(bodies, dtype=np.uint64).ravel()
+    _check_rows(output_list, b.size, output_list.shape[-1] - 1)
+    src = LweSource("seeded_list", output_list.shape[-1] - 1, b, seeds=int(compression_seed))
+    output_list[...] = engine.lwe_expand(src).reshape(output_list.shape)
+
+
+def decompress_seeded_lwe_ciphertext(output_ct: np.ndarray, body: int, compression_seed: int, engine: Engine) -> None:
+    """output [n+1] <- a SeededLweCiphertext (one body word and its CompressionSeed)"""
+    _check_rows(output_ct, 1, output_ct.shape[-1] - 1)
+    src = LweSource("seeded_rows", output_ct.shape[-1] - 1, np.array([body], dtype=np.uint64), seeds=[int(compression_seed)])
+    output_ct[...] = engine.lwe_expand(src).reshape(output_ct.shape)

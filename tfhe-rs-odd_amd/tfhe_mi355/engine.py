@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import TfheMi355Parameters, sz, u32p, u64p, vp
+from ._lib import TfheMi355LweSource, TfheMi355Parameters, sz, u32p, u64p, vp
 from .parameters import ClassicPBSParameters
 
 
@@ -74,6 +74,51 @@ def pinned_empty(shape, dtype=np.uint64) -> np.ndarray:
     buf = (ctypes.c_uint8 * max(n, 1)).from_address(p.value)
     weakref.finalize(buf, _free_host, p.value)
     return np.frombuffer(buf, dtype=np.uint8, count=n).view(dtype).reshape(shape)
+
+
+class LweSource:
+    """Where LWE rows come from (TfheMi355LweSource): kind "rows" ([count][n+1] expanded rows), "compact"
+    (the container of an LweCompactCiphertextList), "seeded_list" (bodies + one 128-bit seed) or "seeded_rows"
+    (bodies + one seed per row).  data and seeds are numpy arrays (host-pointer calls) or torch device tensors
+    (async calls); seeds as Python ints are packed into {lo, hi} words."""
+    KINDS = {"rows": 0, "compact": 1, "seeded_list": 2, "seeded_rows": 3}
+
+    def __init__(self, kind, lwe_dimension: int, data, seeds=None, count=None):
+        self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        self.lwe_dimension = int(lwe_dimension)
+        host = not hasattr(data, "data_ptr")
+        self.data = _u64(data).ravel() if host else data
+        if seeds is not None and not hasattr(seeds, "data_ptr"):
+            if isinstance(seeds, np.ndarray) and seeds.dtype == np.uint64:  # {lo, hi} words already
+                seeds = np.ascontiguousarray(seeds).ravel()
+            else:
+                ints = [seeds] if isinstance(seeds, (int, np.integer)) else list(seeds)
+                seeds = np.array([[int(x) & 0xFFFFFFFFFFFFFFFF, (int(x) >> 64) & 0xFFFFFFFFFFFFFFFF] for x in ints],
+                                 dtype=np.uint64).ravel()
+        self.seeds = seeds
+        n = self.lwe_dimension
+        if count is None:
+            size = self.data.size if host else self.data.numel()
+            if self.kind == 0:
+                count = size // (n + 1)
+            elif self.kind == 1:
+                raise ValueError("a compact source needs its ciphertext count")
+            else:
+                count = size
+        self.count = int(count)
+        if host:
+            need = {0: self.count * (n + 1), 1: -(-self.count // n) * n + self.count}.get(self.kind, self.count)
+            if self.data.size != need:
+                raise ValueError(f"source data has {self.data.size} words, expected {need}")
+            if self.kind in (2, 3) and (self.seeds is None or self.seeds.size != (2 if self.kind == 2 else 2 * self.count)):
+                raise ValueError("seeded source: one {lo, hi} seed for a list, one per row for rows")
+
+    def _c(self) -> TfheMi355LweSource:
+        def p(a):
+            if a is None:
+                return None
+            return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+        return TfheMi355LweSource(self.kind, self.lwe_dimension, p(self.data), p(self.seeds))
 
 
 def device_count() -> int:
@@ -905,6 +950,59 @@ class Engine:
         _lib.call("tfhe_mi355_programmable_bootstrap_keyswitch_async", self._h, _dev_ptr(d_in),
                   _dev_ptr(d_out), _dev_ptr(d_luts), lut_count, _dev_ptr(d_lut_indexes), count,
                   sp, sb, _stream_ptr(stream))
+
+    # -- compressed ciphertext ingress (tfhe_mi355_lwe_expand*, tfhe_mi355_apply_from*) -------------------
+    def lwe_expand(self, source: LweSource) -> np.ndarray:
+        """The expanded rows [count][n+1] of a host source (CompactCiphertextList::expand,
+        CompressedCiphertext::decompress, decompress_seeded_lwe_ciphertext_list), written on the GPU."""
+        out = np.empty((source.count, source.lwe_dimension + 1), dtype=np.uint64)
+        c = source._c()
+        _lib.call("tfhe_mi355_lwe_expand", self._h, ctypes.byref(c), source.count, _ptr(out))
+        return out
+
+    def lwe_expand_scratch_bytes(self, kind: int, lwe_dimension: int, count: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call("tfhe_mi355_lwe_expand_scratch", self._h, kind, lwe_dimension, count, ctypes.byref(b))
+        return b.value
+
+    def lwe_expand_async(self, d_source: LweSource, d_out, stream=None, d_scratch=None) -> None:
+        need = self.lwe_expand_scratch_bytes(d_source.kind, d_source.lwe_dimension, d_source.count)
+        sp, sb, _keep = self._scratch(d_scratch, need, stream)
+        c = d_source._c()
+        _lib.call("tfhe_mi355_lwe_expand_async", self._h, ctypes.byref(c), d_source.count, _dev_ptr(d_out), sp, sb,
+                  _stream_ptr(stream))
+
+    def apply_from(self, op: str, source: LweSource, luts=None, lut_indexes=None, out=None) -> np.ndarray:
+        """`op` ("pbs", "ks_pbs", "pbs_ks", "ks") on the rows of a host source, expanded on the GPU chunk by
+        chunk: the outputs of lwe_expand followed by the operation's own call, bit for bit.  `out` (optional):
+        the caller's output array (one from `pinned_empty` is DMA'd into directly)."""
+        code, _din, dout = self.OPS[op]
+        w_out = (self.n if dout == "n" else self.big_dim) + 1
+        count = source.count
+        if code == 3:
+            L, idxp, nl = None, None, 0
+        else:
+            L = self._luts(luts)
+            idx, idxp = self._idx(lut_indexes, count, L.shape[0])
+            nl = L.shape[0]
+        out = self._out(out, (count, w_out))
+        c = source._c()
+        _lib.call("tfhe_mi355_apply_from", self._h, code, ctypes.byref(c), _ptr(out), None if L is None else _ptr(L),
+                  nl, idxp, count)
+        return out
+
+    def apply_from_scratch_bytes(self, op: str, kind: int, count: int) -> int:
+        b = ctypes.c_size_t()
+        _lib.call("tfhe_mi355_apply_from_scratch", self._h, self.OPS[op][0], kind, count, ctypes.byref(b))
+        return b.value
+
+    def apply_from_async(self, op: str, d_source: LweSource, d_out, d_luts=None, lut_count: int = 0,
+                         d_lut_indexes=None, stream=None, d_scratch=None) -> None:
+        need = self.apply_from_scratch_bytes(op, d_source.kind, d_source.count)
+        sp, sb, _keep = self._scratch(d_scratch, need, stream)
+        c = d_source._c()
+        _lib.call("tfhe_mi355_apply_from_async", self._h, self.OPS[op][0], ctypes.byref(c), _dev_ptr(d_out),
+                  _dev_ptr(d_luts), lut_count, _dev_ptr(d_lut_indexes), d_source.count, sp, sb, _stream_ptr(stream))
 
     def lwe_scalar_mul_add_async(self, y_ptr: int, x_ptr, scalar: int, rows: int, words: int, y_stride: int,
                                  x_stride: int = 0, stream=None) -> None:

@@ -2,6 +2,8 @@
 authoritative -- see SURVEY.md 0.4 for the BASELINE.json annotation mismatch).
 
   PARAM_MESSAGE_<m>_CARRY_<c>_{KS_PBS,PBS_KS}   shortint/parameters/mod.rs:598-1201 (every set; table below)
+  PARAM_MESSAGE_<m>_CARRY_<c>_COMPACT_PK_{KS_PBS,PBS_KS}   shortint/parameters/parameters_compact_pk.rs (all 56:
+                                   COMPACT_PK_ALL, the accepted ones; COMPACT_PK_REFUSED, the others)
   PARAM_MESSAGE_2_CARRY_2_KS_PBS   shortint/parameters/mod.rs:703-717 (alias :1256)
   PARAM_MESSAGE_4_CARRY_4_KS_PBS   shortint/parameters/mod.rs:1063-1077 (alias :1271)
   PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_3_KS_PBS   shortint/parameters/multi_bit.rs:173-190
@@ -260,6 +262,157 @@ ALL = {p.name: p for p in [PARAM_MESSAGE_2_CARRY_2_KS_PBS, PARAM_MESSAGE_4_CARRY
                            PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_2_KS_PBS, MANTICORE_PARAMETERS] + GADGET_ALL}
 ALL.update(SHORTINT_ALL)
 ALL.update(MULTI_BIT_ALL)
+
+
+# The compact-public-key sets (shortint/parameters/parameters_compact_pk.rs:13-70, all 56): the dimension of the
+# encryption key (k N for KS_PBS, n for PBS_KS) is a power of two, as a CompactPublicKey needs.  Same columns as
+# _SHORTINT_TABLE.  Kept apart from ALL: COMPACT_PK_ALL holds the sets the engine accepts (context creation
+# succeeds and an existing keyswitch arm takes the keyswitch decomposition), COMPACT_PK_REFUSED names every other
+# one with the engine's refusal.
+_COMPACT_PK_TABLE = [
+    ("PARAM_MESSAGE_1_CARRY_1_COMPACT_PK_KS_PBS", 71, 638, 1, 1024, 6.150656787521441e-05, 4.9902938117294516e-08,
+     6, 3, 2, 6, 2, 2, "Big"),
+    ("PARAM_MESSAGE_1_CARRY_2_COMPACT_PK_KS_PBS", 86, 710, 1, 2048, 1.6307554775887557e-05, 3.152834667799722e-16,
+     21, 1, 3, 4, 2, 4, "Big"),
+    ("PARAM_MESSAGE_1_CARRY_3_COMPACT_PK_KS_PBS", 101, 756, 1, 2048, 6.983104533665408e-06, 3.152834667799722e-16,
+     21, 1, 3, 5, 2, 8, "Big"),
+    ("PARAM_MESSAGE_1_CARRY_4_COMPACT_PK_KS_PBS", 116, 821, 1, 4096, 2.1066761751849058e-06, 2.168404344971009e-19,
+     22, 1, 3, 5, 2, 16, "Big"),
+    ("PARAM_MESSAGE_1_CARRY_5_COMPACT_PK_KS_PBS", 131, 888, 1, 8192, 6.12494404462554e-07, 2.168404344971009e-19,
+     22, 1, 3, 6, 2, 32, "Big"),
+    ("PARAM_MESSAGE_1_CARRY_6_COMPACT_PK_KS_PBS", 146, 942, 1, 16384, 2.2630942423569665e-07, 2.168404344971009e-19,
+     14, 2, 3, 6, 2, 64, "Big"),
+    ("PARAM_MESSAGE_1_CARRY_7_COMPACT_PK_KS_PBS", 161, 1029, 1, 32768, 4.5508144326041556e-08, 2.168404344971009e-19,
+     14, 2, 4, 5, 2, 128, "Big"),
+    ("PARAM_MESSAGE_2_CARRY_1_COMPACT_PK_KS_PBS", 176, 710, 1, 2048, 1.6307554775887557e-05, 3.152834667799722e-16,
+     22, 1, 3, 4, 4, 2, "Big"),
+    ("PARAM_MESSAGE_2_CARRY_2_COMPACT_PK_KS_PBS", 191, 756, 1, 2048, 6.983104533665408e-06, 3.152834667799722e-16,
+     22, 1, 3, 5, 4, 4, "Big"),
+    ("PARAM_MESSAGE_2_CARRY_3_COMPACT_PK_KS_PBS", 206, 850, 1, 4096, 1.2341934723690542e-06, 2.168404344971009e-19,
+     22, 1, 4, 4, 4, 8, "Big"),
+    ("PARAM_MESSAGE_2_CARRY_4_COMPACT_PK_KS_PBS", 221, 877, 1, 8192, 7.502111286917793e-07, 2.168404344971009e-19,
+     14, 2, 3, 6, 4, 16, "Big"),
+    ("PARAM_MESSAGE_2_CARRY_5_COMPACT_PK_KS_PBS", 236, 942, 1, 16384, 2.2630942423569665e-07, 2.168404344971009e-19,
+     14, 2, 3, 6, 4, 32, "Big"),
+    ("PARAM_MESSAGE_2_CARRY_6_COMPACT_PK_KS_PBS", 251, 1030, 1, 32768, 4.46767660406645e-08, 2.168404344971009e-19,
+     14, 2, 4, 5, 4, 64, "Big"),
+    ("PARAM_MESSAGE_3_CARRY_1_COMPACT_PK_KS_PBS", 266, 759, 1, 2048, 6.607793351104514e-06, 3.152834667799722e-16,
+     23, 1, 3, 5, 8, 2, "Big"),
+    ("PARAM_MESSAGE_3_CARRY_2_COMPACT_PK_KS_PBS", 281, 862, 1, 4096, 9.892236038140916e-07, 2.168404344971009e-19,
+     22, 1, 3, 6, 8, 4, "Big"),
+    ("PARAM_MESSAGE_3_CARRY_3_COMPACT_PK_KS_PBS", 296, 877, 1, 8192, 7.502111286917793e-07, 2.168404344971009e-19,
+     14, 2, 3, 6, 8, 8, "Big"),
+    ("PARAM_MESSAGE_3_CARRY_4_COMPACT_PK_KS_PBS", 311, 942, 1, 16384, 2.2630942423569665e-07, 2.168404344971009e-19,
+     14, 2, 3, 6, 8, 16, "Big"),
+    ("PARAM_MESSAGE_3_CARRY_5_COMPACT_PK_KS_PBS", 326, 1032, 1, 32768, 4.305929680023812e-08, 2.168404344971009e-19,
+     14, 2, 4, 5, 8, 32, "Big"),
+    ("PARAM_MESSAGE_4_CARRY_1_COMPACT_PK_KS_PBS", 341, 820, 1, 4096, 2.145878762605306e-06, 2.168404344971009e-19,
+     14, 2, 3, 5, 16, 2, "Big"),
+    ("PARAM_MESSAGE_4_CARRY_2_COMPACT_PK_KS_PBS", 356, 877, 1, 8192, 7.502111286917793e-07, 2.168404344971009e-19,
+     14, 2, 3, 6, 16, 4, "Big"),
+    ("PARAM_MESSAGE_4_CARRY_3_COMPACT_PK_KS_PBS", 371, 943, 1, 16384, 2.2219042764335445e-07, 2.168404344971009e-19,
+     15, 2, 3, 6, 16, 8, "Big"),
+    ("PARAM_MESSAGE_4_CARRY_4_COMPACT_PK_KS_PBS", 386, 1044, 1, 32768, 3.4512638181977925e-08, 2.168404344971009e-19,
+     15, 2, 4, 5, 16, 16, "Big"),
+    ("PARAM_MESSAGE_5_CARRY_1_COMPACT_PK_KS_PBS", 401, 877, 1, 8192, 7.502111286917793e-07, 2.168404344971009e-19,
+     15, 2, 3, 6, 32, 2, "Big"),
+    ("PARAM_MESSAGE_5_CARRY_2_COMPACT_PK_KS_PBS", 416, 947, 1, 16384, 2.0639337523302752e-07, 2.168404344971009e-19,
+     15, 2, 3, 6, 32, 4, "Big"),
+    ("PARAM_MESSAGE_5_CARRY_3_COMPACT_PK_KS_PBS", 431, 997, 1, 32768, 8.20967300015962e-08, 2.168404344971009e-19,
+     11, 3, 3, 7, 32, 8, "Big"),
+    ("PARAM_MESSAGE_6_CARRY_1_COMPACT_PK_KS_PBS", 446, 942, 1, 16384, 2.2630942423569665e-07, 2.168404344971009e-19,
+     11, 3, 3, 6, 64, 2, "Big"),
+    ("PARAM_MESSAGE_6_CARRY_2_COMPACT_PK_KS_PBS", 461, 998, 1, 32768, 8.05969228871865e-08, 2.168404344971009e-19,
+     11, 3, 3, 7, 64, 4, "Big"),
+    ("PARAM_MESSAGE_7_CARRY_1_COMPACT_PK_KS_PBS", 476, 1017, 1, 32768, 5.6777713805325606e-08, 2.168404344971009e-19,
+     11, 3, 3, 7, 128, 2, "Big"),
+    ("PARAM_MESSAGE_1_CARRY_1_COMPACT_PK_PBS_KS", 493, 1024, 3, 512, 4.99029381172945e-08, 3.9666940817241e-12,
+     18, 1, 8, 2, 2, 2, "Small"),
+    ("PARAM_MESSAGE_1_CARRY_2_COMPACT_PK_PBS_KS", 508, 1024, 2, 1024, 4.99029381172945e-08, 3.15283466779972e-16,
+     18, 1, 8, 2, 2, 4, "Small"),
+    ("PARAM_MESSAGE_1_CARRY_3_COMPACT_PK_PBS_KS", 523, 1024, 1, 2048, 4.99029381172945e-08, 3.15283466779972e-16,
+     21, 1, 8, 2, 2, 8, "Small"),
+    ("PARAM_MESSAGE_1_CARRY_4_COMPACT_PK_PBS_KS", 538, 1024, 1, 4096, 4.99029381172945e-08, 2.16840434497101e-19,
+     21, 1, 6, 3, 2, 16, "Small"),
+    ("PARAM_MESSAGE_1_CARRY_5_COMPACT_PK_PBS_KS", 553, 1024, 1, 8192, 4.99029381172945e-08, 2.16840434497101e-19,
+     22, 1, 5, 4, 2, 32, "Small"),
+    ("PARAM_MESSAGE_1_CARRY_6_COMPACT_PK_PBS_KS", 568, 1024, 1, 16384, 4.99029381172945e-08, 2.16840434497101e-19,
+     12, 2, 4, 5, 2, 64, "Small"),
+    ("PARAM_MESSAGE_1_CARRY_7_COMPACT_PK_PBS_KS", 583, 1024, 1, 32768, 4.99029381172945e-08, 2.16840434497101e-19,
+     14, 2, 2, 11, 2, 128, "Small"),
+    ("PARAM_MESSAGE_2_CARRY_1_COMPACT_PK_PBS_KS", 598, 1024, 2, 1024, 4.99029381172945e-08, 3.15283466779972e-16,
+     21, 1, 8, 2, 4, 2, "Small"),
+    ("PARAM_MESSAGE_2_CARRY_2_COMPACT_PK_PBS_KS", 613, 1024, 1, 2048, 4.99029381172945e-08, 3.15283466779972e-16,
+     21, 1, 8, 2, 4, 4, "Small"),
+    ("PARAM_MESSAGE_2_CARRY_3_COMPACT_PK_PBS_KS", 628, 1024, 1, 4096, 4.99029381172945e-08, 2.16840434497101e-19,
+     21, 1, 6, 3, 4, 8, "Small"),
+    ("PARAM_MESSAGE_2_CARRY_4_COMPACT_PK_PBS_KS", 643, 1024, 1, 8192, 4.99029381172945e-08, 2.16840434497101e-19,
+     12, 2, 5, 4, 4, 16, "Small"),
+    ("PARAM_MESSAGE_2_CARRY_5_COMPACT_PK_PBS_KS", 658, 1024, 1, 16384, 4.99029381172945e-08, 2.16840434497101e-19,
+     14, 2, 3, 7, 4, 32, "Small"),
+    ("PARAM_MESSAGE_2_CARRY_6_COMPACT_PK_PBS_KS", 673, 2048, 1, 65536, 3.15283466779972e-16, 2.16840434497101e-19,
+     14, 2, 25, 1, 4, 64, "Small"),
+    ("PARAM_MESSAGE_3_CARRY_1_COMPACT_PK_PBS_KS", 688, 1024, 1, 2048, 4.99029381172945e-08, 3.15283466779972e-16,
+     22, 1, 6, 3, 8, 2, "Small"),
+    ("PARAM_MESSAGE_3_CARRY_2_COMPACT_PK_PBS_KS", 703, 1024, 1, 4096, 4.99029381172945e-08, 2.16840434497101e-19,
+     12, 2, 5, 4, 8, 4, "Small"),
+    ("PARAM_MESSAGE_3_CARRY_3_COMPACT_PK_PBS_KS", 718, 1024, 1, 8192, 4.99029381172945e-08, 2.16840434497101e-19,
+     12, 2, 3, 7, 8, 8, "Small"),
+    ("PARAM_MESSAGE_3_CARRY_4_COMPACT_PK_PBS_KS", 733, 1024, 1, 16384, 4.99029381172945e-08, 2.16840434497101e-19,
+     14, 2, 1, 22, 8, 16, "Small"),
+    ("PARAM_MESSAGE_3_CARRY_5_COMPACT_PK_PBS_KS", 748, 2048, 1, 65536, 3.15283466779972e-16, 2.16840434497101e-19,
+     14, 2, 25, 1, 8, 32, "Small"),
+    ("PARAM_MESSAGE_4_CARRY_1_COMPACT_PK_PBS_KS", 763, 1024, 1, 4096, 4.99029381172945e-08, 2.16840434497101e-19,
+     12, 2, 2, 11, 16, 2, "Small"),
+    ("PARAM_MESSAGE_4_CARRY_2_COMPACT_PK_PBS_KS", 778, 1024, 1, 8192, 4.99029381172945e-08, 2.16840434497101e-19,
+     9, 3, 1, 21, 16, 4, "Small"),
+    ("PARAM_MESSAGE_4_CARRY_3_COMPACT_PK_PBS_KS", 793, 2048, 1, 32768, 3.15283466779972e-16, 2.16840434497101e-19,
+     14, 2, 25, 1, 16, 8, "Small"),
+    ("PARAM_MESSAGE_4_CARRY_4_COMPACT_PK_PBS_KS", 808, 2048, 1, 65536, 3.15283466779972e-16, 2.16840434497101e-19,
+     11, 3, 25, 1, 16, 16, "Small"),
+    ("PARAM_MESSAGE_5_CARRY_1_COMPACT_PK_PBS_KS", 823, 2048, 1, 16384, 3.15283466779972e-16, 2.16840434497101e-19,
+     14, 2, 25, 1, 32, 2, "Small"),
+    ("PARAM_MESSAGE_5_CARRY_2_COMPACT_PK_PBS_KS", 838, 2048, 1, 32768, 3.15283466779972e-16, 2.16840434497101e-19,
+     14, 2, 25, 1, 32, 4, "Small"),
+    ("PARAM_MESSAGE_5_CARRY_3_COMPACT_PK_PBS_KS", 853, 2048, 1, 65536, 3.15283466779972e-16, 2.16840434497101e-19,
+     11, 3, 25, 1, 32, 8, "Small"),
+    ("PARAM_MESSAGE_6_CARRY_1_COMPACT_PK_PBS_KS", 868, 2048, 1, 32768, 3.15283466779972e-16, 2.16840434497101e-19,
+     11, 3, 25, 1, 64, 2, "Small"),
+    ("PARAM_MESSAGE_6_CARRY_2_COMPACT_PK_PBS_KS", 883, 2048, 1, 65536, 3.15283466779972e-16, 2.16840434497101e-19,
+     11, 3, 17, 2, 64, 4, "Small"),
+    ("PARAM_MESSAGE_7_CARRY_1_COMPACT_PK_PBS_KS", 898, 2048, 1, 65536, 3.15283466779972e-16, 2.16840434497101e-19,
+     9, 4, 17, 2, 128, 2, "Small"),
+]
+
+# (name, the engine's refusal): context creation finds no PBS kernel at N = 65536; the context's keyswitch fails its
+# launch for ks_base_log > 7 (8 x 2, 17 x 2, 25 x 1: its int8-MFMA and int8 scalar arms hold digits of at most 7 bits;
+# the 16-bit-digit scalar form serves key objects only)
+COMPACT_PK_REFUSED = (
+    ("PARAM_MESSAGE_1_CARRY_1_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_1_CARRY_2_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_1_CARRY_3_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_2_CARRY_1_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_2_CARRY_2_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_2_CARRY_6_COMPACT_PK_PBS_KS", "no kernel for N=65536 k=1 pbs_level=2"),
+    ("PARAM_MESSAGE_3_CARRY_5_COMPACT_PK_PBS_KS", "no kernel for N=65536 k=1 pbs_level=2"),
+    ("PARAM_MESSAGE_4_CARRY_3_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_4_CARRY_4_COMPACT_PK_PBS_KS", "no kernel for N=65536 k=1 pbs_level=3"),
+    ("PARAM_MESSAGE_5_CARRY_1_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_5_CARRY_2_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_5_CARRY_3_COMPACT_PK_PBS_KS", "no kernel for N=65536 k=1 pbs_level=3"),
+    ("PARAM_MESSAGE_6_CARRY_1_COMPACT_PK_PBS_KS", "launch keyswitch: invalid argument"),
+    ("PARAM_MESSAGE_6_CARRY_2_COMPACT_PK_PBS_KS", "no kernel for N=65536 k=1 pbs_level=3"),
+    ("PARAM_MESSAGE_7_CARRY_1_COMPACT_PK_PBS_KS", "no kernel for N=65536 k=1 pbs_level=4"),
+)
+COMPACT_PK_NAMES = tuple(t[0] for t in _COMPACT_PK_TABLE)
+COMPACT_PK_ALL = {
+    t[0]: ClassicPBSParameters(lwe_dimension=t[2], glwe_dimension=t[3], polynomial_size=t[4], lwe_modular_std_dev=t[5],
+                               glwe_modular_std_dev=t[6], pbs_base_log=t[7], pbs_level=t[8], ks_base_log=t[9],
+                               ks_level=t[10], message_modulus=t[11], carry_modulus=t[12], encryption_key_choice=t[13],
+                               name=t[0])
+    for t in _COMPACT_PK_TABLE if t[0] not in dict(COMPACT_PK_REFUSED)}
+COMPACT_PK_SOURCE_LINE = {t[0]: t[1] for t in _COMPACT_PK_TABLE}
+globals().update(COMPACT_PK_ALL)
 
 
 @dataclass(frozen=True)

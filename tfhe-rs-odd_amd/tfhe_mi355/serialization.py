@@ -12,6 +12,10 @@ reference's types on the host:
     tfhe-rs client produces, so that keys made by this engine's client side can be shipped the
     same way (and the reader tested without a Rust toolchain).
 
+The two compressed ciphertext types a client uploads travel the same way: `inspect_compact_ciphertext_list` /
+`inspect_compressed_ciphertext` -> `CiphertextInfo`, `serialize_compact_ciphertext_list` /
+`serialize_compressed_ciphertext` the writers (shortint/ciphertext/mod.rs:467-476, 521-529).
+
 bincode default options: little-endian fixed-width integers, usize = u64, u128 = low then high
 u64, Vec / serialize_seq = u64 length + elements, enum variant = u32 index, bool = 1 byte,
 newtype structs (LweSize(usize), ...) = their field.
@@ -167,3 +171,63 @@ def serialize_server_key(p: ClassicPBSParameters, ksk, fourier_bsk, max_degree: 
             _u64(_default_max_degree(p) if max_degree is None else max_degree), _u64(max_noise_level),
             _modulus(), _u32(order)]
     return b"".join(out)
+
+
+# ---- compressed ciphertexts ----------------------------------------------------------------------
+
+@dataclass
+class CiphertextInfo:
+    """What a serialized CompactCiphertextList / CompressedCiphertext holds (TfheMi355CiphertextInfo):
+    data_offset / data_words locate the u64 container (compact) or the body word inside the bytes."""
+
+    lwe_dimension: int
+    count: int
+    degree: int
+    message_modulus: int
+    carry_modulus: int
+    pbs_order: int
+    noise_level: int
+    data_offset: int
+    data_words: int
+    seed: int   # CompressionSeed of a CompressedCiphertext, else 0
+
+    def words(self, data: bytes) -> np.ndarray:
+        """the container's words, copied out (bincode does not align them)"""
+        return np.frombuffer(data, dtype="<u8", count=self.data_words, offset=self.data_offset).astype(np.uint64)
+
+
+def _ct_info(fn: str, data: bytes) -> CiphertextInfo:
+    buf = np.frombuffer(data, dtype=np.uint8)
+    out = _lib.TfheMi355CiphertextInfo()
+    _lib.call(fn, buf.ctypes.data_as(_lib.u8p), buf.size, ctypes.byref(out))
+    return CiphertextInfo(out.lwe_dimension, out.count, out.degree, out.message_modulus, out.carry_modulus,
+                          out.pbs_order, out.noise_level, out.data_offset, out.data_words,
+                          out.seed_lo | (out.seed_hi << 64))
+
+
+def inspect_compact_ciphertext_list(data: bytes) -> CiphertextInfo:
+    return _ct_info("tfhe_mi355_compact_ciphertext_list_inspect", data)
+
+
+def inspect_compressed_ciphertext(data: bytes) -> CiphertextInfo:
+    return _ct_info("tfhe_mi355_compressed_ciphertext_inspect", data)
+
+
+def _ct_tail(degree, message_modulus, carry_modulus, pbs_order, noise_level):
+    return [_u64(degree), _u64(message_modulus), _u64(carry_modulus), _u32(pbs_order), _u64(noise_level)]
+
+
+def serialize_compact_ciphertext_list(container, lwe_dimension: int, count: int, degree: int, message_modulus: int,
+                                      carry_modulus: int, pbs_order: int, noise_level: int = 1) -> bytes:
+    """CompactCiphertextList: LweCompactCiphertextList{data, lwe_size, lwe_ciphertext_count, ciphertext_modulus}
+    (entities/lwe_compact_ciphertext_list.rs:19-27), then the shortint fields."""
+    out = [_vec_u64(container), _u64(lwe_dimension + 1), _u64(count), _modulus()]
+    return b"".join(out + _ct_tail(degree, message_modulus, carry_modulus, pbs_order, noise_level))
+
+
+def serialize_compressed_ciphertext(body: int, lwe_dimension: int, seed: int, degree: int, message_modulus: int,
+                                    carry_modulus: int, pbs_order: int, noise_level: int = 1) -> bytes:
+    """CompressedCiphertext: SeededLweCiphertext{data: u64, lwe_size, compression_seed, ciphertext_modulus}
+    (entities/seeded_lwe_ciphertext.rs:13-18), then the shortint fields."""
+    out = [_u64(int(body)), _u64(lwe_dimension + 1), _u128(seed), _modulus()]
+    return b"".join(out + _ct_tail(degree, message_modulus, carry_modulus, pbs_order, noise_level))

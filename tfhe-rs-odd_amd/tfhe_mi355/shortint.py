@@ -17,6 +17,11 @@
   WopbsKey.keyswitch_to_wopbs_params / keyswitch_to_pbs_params / programmable_bootstrapping /
   extract_bits / circuit_bootstrapping_vertical_packing     wopbs/mod.rs:398-408, 547-754
 
+  CompactPublicKey.encrypt_many                             public_key/compact.rs (CompactPublicKey::encrypt_slice)
+  CompactCiphertextList.expand                              ciphertext/mod.rs:544-584
+  CompressedCiphertext.decompress                           ciphertext/mod.rs:493-513
+  ClientKey.encrypt_compressed_many                         engine/client_side.rs (encrypt_compressed)
+
 Batched forms (`apply_lookup_table_batch`) hand a whole layer of independent ciphertexts to the
 GPU in one launch -- the shape the integer layer produces (radix_parallel/mul.rs:347-407).
 """
@@ -28,7 +33,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import client
-from .engine import Engine, fill_accumulator
+from .engine import Engine, LweSource, fill_accumulator
 from .parameters import ClassicPBSParameters, WopbsParameters
 
 NOISE_ZERO = 0
@@ -102,6 +107,19 @@ class ClientKey:
     def encrypt(self, message: int) -> Ciphertext:
         return self.encrypt_many([message])[0]
 
+    def encrypt_compressed_many(self, messages) -> list["CompressedCiphertext"]:
+        """One CompressedCiphertext per message, each under a CompressionSeed of its own (derived from the key's
+        seed and a counter; the reference draws it from its seeder)."""
+        p = self.parameters
+        m = np.asarray(messages, dtype=np.uint64) % np.uint64(p.message_modulus)
+        key, std = self._enc_key()
+        self._enc_counter += 1
+        base = ((self.seed << 20) + self._enc_counter) << 64
+        seeds = [(base + i) * 0x9E3779B97F4A7C15F39CC0605CEDC835 % (1 << 128) for i in range(len(m))]
+        bodies = client.seeded_lwe_encrypt((self.seed << 20) + self._enc_counter, seeds, key, m * np.uint64(p.delta), std)
+        return [CompressedCiphertext(int(bodies[i]), seeds[i], len(key), p.message_modulus - 1, NOISE_NOMINAL,
+                                     p.message_modulus, p.carry_modulus, self.pbs_order) for i in range(len(m))]
+
     def decrypt_message_and_carry_many(self, cts: list[Ciphertext]) -> np.ndarray:
         key = self.large_lwe_secret_key if cts[0].pbs_order == KEYSWITCH_BOOTSTRAP else self.small_lwe_secret_key
         raw = client.lwe_decrypt(key, np.stack([c.ct for c in cts]))
@@ -136,6 +154,129 @@ class ClientKey:
 
     def decrypt_without_padding(self, ct: Ciphertext) -> int:
         return self.decrypt_message_and_carry_without_padding(ct) % ct.message_modulus
+
+
+def _order_code(pbs_order: str) -> int:
+    return 0 if pbs_order == KEYSWITCH_BOOTSTRAP else 1
+
+
+def _order_name(code: int) -> str:
+    return KEYSWITCH_BOOTSTRAP if code == 0 else BOOTSTRAP_KEYSWITCH
+
+
+def _engine_of(where) -> Engine:
+    return where.engine if hasattr(where, "engine") else where
+
+
+@dataclass
+class CompressedCiphertext:
+    """shortint CompressedCiphertext (ciphertext/mod.rs:467-476): a SeededLweCiphertext -- one body word and the
+    CompressionSeed of its mask."""
+
+    body: int
+    seed: int
+    lwe_dimension: int
+    degree: int
+    noise_level: int
+    message_modulus: int
+    carry_modulus: int
+    pbs_order: str
+
+    def decompress(self, where) -> Ciphertext:
+        """The full ciphertext, its mask regenerated on the GPU of `where` (an Engine or a ServerKey)."""
+        return decompress_many([self], where)[0]
+
+    def serialize(self) -> bytes:
+        from .serialization import serialize_compressed_ciphertext
+
+        return serialize_compressed_ciphertext(self.body, self.lwe_dimension, self.seed, self.degree, self.message_modulus,
+                                               self.carry_modulus, _order_code(self.pbs_order), self.noise_level)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "CompressedCiphertext":
+        from .serialization import inspect_compressed_ciphertext
+
+        i = inspect_compressed_ciphertext(data)
+        return cls(int(i.words(data)[0]), i.seed, i.lwe_dimension, i.degree, i.noise_level, i.message_modulus,
+                   i.carry_modulus, _order_name(i.pbs_order))
+
+
+def _compressed_source(cts: list[CompressedCiphertext]) -> LweSource:
+    n = cts[0].lwe_dimension
+    if any(c.lwe_dimension != n for c in cts):
+        raise ValueError("compressed ciphertexts of different LweSize")
+    return LweSource("seeded_rows", n, np.array([c.body for c in cts], dtype=np.uint64), seeds=[c.seed for c in cts])
+
+
+def decompress_many(cts: list[CompressedCiphertext], where) -> list[Ciphertext]:
+    rows = _engine_of(where).lwe_expand(_compressed_source(cts))
+    return [Ciphertext(rows[i].copy(), c.degree, c.noise_level, c.message_modulus, c.carry_modulus, c.pbs_order)
+            for i, c in enumerate(cts)]
+
+
+@dataclass
+class CompactCiphertextList:
+    """shortint CompactCiphertextList (ciphertext/mod.rs:521-529): an LweCompactCiphertextList container
+    ([ceil(count / n)][n] masks, then [count] bodies) and the fields every ciphertext of it gets."""
+
+    container: np.ndarray
+    lwe_dimension: int
+    count: int
+    degree: int
+    noise_level: int
+    message_modulus: int
+    carry_modulus: int
+    pbs_order: str
+
+    def __len__(self):
+        return self.count
+
+    def source(self) -> LweSource:
+        return LweSource("compact", self.lwe_dimension, self.container, count=self.count)
+
+    def expand(self, where) -> list[Ciphertext]:
+        """The ciphertexts, expanded on the GPU of `where` (an Engine or a ServerKey)."""
+        rows = _engine_of(where).lwe_expand(self.source())
+        return [Ciphertext(rows[i].copy(), self.degree, self.noise_level, self.message_modulus, self.carry_modulus,
+                           self.pbs_order) for i in range(self.count)]
+
+    def serialize(self) -> bytes:
+        from .serialization import serialize_compact_ciphertext_list
+
+        return serialize_compact_ciphertext_list(self.container, self.lwe_dimension, self.count, self.degree,
+                                                 self.message_modulus, self.carry_modulus, _order_code(self.pbs_order),
+                                                 self.noise_level)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "CompactCiphertextList":
+        from .serialization import inspect_compact_ciphertext_list
+
+        i = inspect_compact_ciphertext_list(data)
+        return cls(i.words(data), i.lwe_dimension, i.count, i.degree, i.noise_level, i.message_modulus, i.carry_modulus,
+                   _order_name(i.pbs_order))
+
+
+class CompactPublicKey:
+    """shortint CompactPublicKey (public_key/compact.rs): an LweCompactPublicKey of the client key's encryption key
+    (the big key for KS -> PBS sets, the small one for PBS -> KS sets); its dimension must be a power of two."""
+
+    def __init__(self, client_key: ClientKey):
+        self.parameters = client_key.parameters
+        self.pbs_order = client_key.pbs_order
+        key, self.std_dev = client_key._enc_key()
+        self.lwe_dimension = len(key)
+        self.seed = client_key.seed
+        self._counter = 0
+        self.key = client.gen_compact_public_key(client_key.seed * 7 + 5, key, self.std_dev)
+
+    def encrypt_many(self, messages) -> CompactCiphertextList:
+        p = self.parameters
+        m = np.asarray(messages, dtype=np.uint64) % np.uint64(p.message_modulus)
+        self._counter += 1
+        box = client.compact_encrypt((self.seed << 20) + (1 << 19) + self._counter, self.key, m * np.uint64(p.delta),
+                                     self.std_dev)
+        return CompactCiphertextList(box, self.lwe_dimension, len(m), p.message_modulus - 1, NOISE_NOMINAL,
+                                     p.message_modulus, p.carry_modulus, self.pbs_order)
 
 
 class ServerKey:
@@ -248,7 +389,31 @@ class ServerKey:
         for i, c in enumerate(cts):
             c.degree = accs[i].degree
 
-    def apply_lookup_table_batch(self, cts: list[Ciphertext], accs) -> list[Ciphertext]:
+    def _apply_from(self, source: LweSource, like, accs) -> list[Ciphertext]:
+        """a compressed source straight through the key's PBS order (Engine.apply_from): the rows are expanded on
+        the GPU, chunk by chunk, where the copy of expanded rows would have landed"""
+        count = source.count
+        if isinstance(accs, LookupTable):
+            accs = [accs] * count
+        uniq, idx = {}, []
+        for a in accs:
+            if id(a) not in uniq:
+                uniq[id(a)] = (len(uniq), a.acc)
+            idx.append(uniq[id(a)][0])
+        luts = np.stack([a for _, a in sorted(uniq.values(), key=lambda t: t[0])])
+        lut_idx = np.asarray(idx, dtype=np.uint32) if len(uniq) > 1 else None
+        op = "ks_pbs" if self.pbs_order == KEYSWITCH_BOOTSTRAP else "pbs_ks"
+        out = self.engine.apply_from(op, source, luts, lut_idx)
+        return [Ciphertext(out[i].copy(), accs[i].degree, NOISE_NOMINAL, like(i).message_modulus, like(i).carry_modulus,
+                           self.pbs_order) for i in range(count)]
+
+    def apply_lookup_table_batch(self, cts, accs) -> list[Ciphertext]:
+        """cts: a list of Ciphertext, or -- compressed ingress -- a CompactCiphertextList or a list of
+        CompressedCiphertext, which go to the GPU in their compressed form."""
+        if isinstance(cts, CompactCiphertextList):
+            return self._apply_from(cts.source(), lambda i: cts, accs) if cts.count else []
+        if len(cts) and all(isinstance(c, CompressedCiphertext) for c in cts):
+            return self._apply_from(_compressed_source(cts), lambda i: cts[i], accs)
         res = [c.clone() for c in cts]
         self.apply_lookup_table_batch_assign(res, accs)
         return res
