@@ -58,7 +58,17 @@
  *     given less than its query fails with an error, and only a query returning 0 allows
  *     d_scratch = NULL), so concurrent callers on different streams only need scratch buffers
  *     of their own, and the calls can be captured into a hipGraph (no allocation or
- *     synchronisation inside);
+ *     synchronisation inside).  Two forms are the exception:
+ *     tfhe_mi355_bootstrap_key_convert_async and tfhe_mi355_keyswitch_key_upload_async wait for
+ *     their stream before they return (see "keys uploaded through the _async/device forms" below),
+ *     so they refuse a capturing stream: rc 1 and a message naming stream capture, before anything
+ *     is locked, marked not ready or enqueued -- the caller's capture stays valid and the resident
+ *     key is untouched; upload keys outside the graph.  No warm-up is needed: the first call of a
+ *     form on a context may be the captured one (an _async call initialises nothing lazily).
+ *     The per-device serialisation of quad CMUX launches does not extend to captured graphs: the
+ *     launcher skips its cross-stream event chain while the stream is being captured, so a replay
+ *     is ordered against nothing.  Do not replay a graph that holds a quad CMUX while another quad
+ *     launch, eager or replayed, may run on the same GPU;
  *   - every device pointer handed to an _async entry point (inputs, outputs, LUTs, index and opcode
  *     arrays, Fourier GGSW lists, key sources, d_scratch) must be 16-byte aligned at its base; rows
  *     inside a buffer follow from the row lengths (8-byte alignment for u64 rows, 4 for u32 rows, 16

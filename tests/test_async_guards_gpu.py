@@ -102,7 +102,9 @@ def _spec(regions, call, twin, out, scratch, kernels, oracle=None, out_row=None)
     """regions: the arena's declaration, in address order; call(v): the async call on the views v[name];
     twin(): the expected bytes of region `out` (an array); scratch: (region name or None, the queried
     size); kernels: timer families that must have run (None: the entry point has no timer family);
-    oracle(): (rows, expected [rows][words]) of the sampled rows from a reference of its own."""
+    oracle(): (rows, expected [rows][words]) of the sampled rows from a reference of its own.
+    A case may set spec.primary afterwards: the region holding its primary ciphertext input, where that is not
+    the first read-only ciphertext region (tests/test_async_graph_gpu.py changes it between replays)."""
     return NS(regions=regions, call=call, twin=twin, out=out, scratch=scratch, kernels=kernels, oracle=oracle,
               out_row=out_row)
 
@@ -898,7 +900,10 @@ for _scalar in (3, 2 ** 64 - 1):
                 eng.lwe_scalar_mul_add_async(y + 8 * 3 * WORDS, xp, scalar, 3, WORDS, 5 * WORDS, xs)
 
             regions = [_rin("x", X, row=WORDS * 8), _rout("out", Y.nbytes, row=WORDS * 8, data=Y)]
-            return _spec(regions, call, lambda: exp, "out", (None, 0), None, out_row=5 * WORDS * 8)
+            spec = _spec(regions, call, lambda: exp, "out", (None, 0), None, out_row=5 * WORDS * 8)
+            if src != "other":  # x is not read here: the ciphertext input is y's own tensor
+                spec.primary = "out"
+            return spec
 
 
 @case("trivial_pbs-257", "c2048", ["trivial_pbs_async"])
@@ -945,6 +950,26 @@ def _run_call(spec, arena, views):
     return out, changed
 
 
+def build_arena(spec):
+    """(arena, views) of a case: every region of the spec at 16 modulo 256, the scratch of exactly the queried
+    size (test_async_graph_gpu.py replays the cases from arenas built here)"""
+    # 3. the scratch: exactly the queried size, or none where the query says 0
+    sname, need = spec.scratch
+    names = [r.name for r in spec.regions]
+    if need == 0:
+        assert sname is None and "scratch" not in names
+    else:
+        assert [r.nbytes for r in spec.regions if r.name == sname] == [need]
+    arena = GuardedArena("cuda:0", seed=1)
+    for r in spec.regions:
+        arena.region(r.name, r.nbytes, align=16, data=r.data, writable=r.writable, row=r.row)
+    arena.allocate()
+    views = {r.name: arena.view(r.name) for r in spec.regions}
+    for v in views.values():
+        assert v.data_ptr() % 256 == 16
+    return arena, views
+
+
 @pytest.mark.parametrize("c", CASES, ids=lambda c: c.id)
 def test_guarded_call(orc, c):
     E = _engine(c.engine, orc)
@@ -952,20 +977,8 @@ def test_guarded_call(orc, c):
         spec = c.build(E, orc)
         eng = E.eng
         expected = np.ascontiguousarray(spec.twin()).view(np.uint8).reshape(-1)
-        # 3. the scratch: exactly the queried size, or none where the query says 0
-        sname, need = spec.scratch
-        names = [r.name for r in spec.regions]
-        if need == 0:
-            assert sname is None and "scratch" not in names
-        else:
-            assert [r.nbytes for r in spec.regions if r.name == sname] == [need]
-        arena = GuardedArena("cuda:0", seed=1)
-        for r in spec.regions:
-            arena.region(r.name, r.nbytes, align=16, data=r.data, writable=r.writable, row=r.row)
-        arena.allocate()
-        views = {r.name: arena.view(r.name) for r in spec.regions}
-        for v in views.values():
-            assert v.data_ptr() % 256 == 16
+        need = spec.scratch[1]
+        arena, views = build_arena(spec)
         # first call, under the kernel timer
         eng.kernel_timing(1)
         out1, changed1 = _run_call(spec, arena, views)

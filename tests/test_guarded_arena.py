@@ -182,3 +182,26 @@ def test_every_async_entry_point_has_a_guarded_case_or_a_reason():
         assert n in names, f"{n} is not an _async entry point of the header"
     for n, why in G.EXCLUDED.items():
         assert isinstance(why, str) and len(why) > 20, n
+
+
+def test_every_guarded_entry_point_is_replayed_from_a_graph_or_documented_as_waiting():
+    """tests/test_async_graph_gpu.py replays the guarded cases (the ingress cases among them: it imports both case
+    modules) from captured graphs: every entry point with a guarded case has a replayed one, or stands in
+    NOT_CAPTURABLE under a sentence of the header that says the call waits -- never both."""
+    import test_async_graph_gpu as R
+    import test_async_guards_gpu as G
+
+    covered = G.covered_entry_points()
+    assert "tfhe_mi355_lwe_expand_async" in covered and "tfhe_mi355_apply_from_async" in covered
+    replayed = R.replayed_entry_points()
+    assert len({c.id for c in R.CASES}) == len(R.CASES) == len(G.CASES)
+    for n in covered:
+        assert (n in replayed) != (n in R.NOT_CAPTURABLE), f"{n}: needs a replayed case or a header sentence (not both)"
+    for n in list(replayed) + list(R.NOT_CAPTURABLE):
+        assert n in covered, f"{n} has no guarded case"
+    with open(os.path.join(ROOT, "include", "tfhe_mi355.h")) as f:
+        header = " ".join(f.read().replace("*", " ").split())
+    for n, sentence in R.NOT_CAPTURABLE.items():
+        assert "waits" in sentence and " ".join(sentence.split()) in header, f"{n}: the header does not say so"
+        at = header.index("refuse a capturing stream")  # the capture paragraph names the forms that do
+        assert n in header[max(at - 400, 0):at], n

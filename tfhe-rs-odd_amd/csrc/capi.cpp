@@ -260,6 +260,15 @@ size_t pbs_ks_scratch_bytes(const TfheMi355Context *c, size_t count) {
     return fused_layout(c, c->big_dim() + 1, count).total();
 }
 
+// The device-pointer key uploads wait for their stream before they return, which a capturing stream cannot
+// do (the wait fails and invalidates the caller's capture): they refuse first, before anything is locked,
+// marked not ready or enqueued.
+void refuse_capture(const char *entry, hipStream_t s) {
+    if (stream_is_capturing(s))
+        fail("%s cannot run under stream capture (the stream is being captured, or its capture state cannot be "
+             "read): the call waits for its stream, so it belongs outside the graph", entry);
+}
+
 void require_scratch(size_t have, size_t need) {
     if (have < need) fail("device scratch too small: %zu bytes given, %zu needed (see the *_scratch queries)", have, need);
 }
@@ -339,7 +348,7 @@ void launch_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, 
     // persistent grid: a zeroed ticket word from the caller's scratch (none given: one pass)
     if (classic_pbs_ticket_bytes((int)c->N(), (int)c->k(), (int)c->p.pbs_level) && scratch && scratch_bytes >= 4) {
         a.ticket = reinterpret_cast<uint32_t *>(scratch);
-        check(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s), "zero pbs ticket");
+        check(launch_zero_words(a.ticket, 1, s), "zero pbs ticket");  // a kernel: it replays from a graph
     }
     TimedLaunch tl(c->timer_or_null(), "pbs_classic_kernel", s);
     check(launch_classic_pbs((int)c->N(), (int)c->k(), (int)c->p.pbs_level, a, s), "launch pbs");
@@ -1981,6 +1990,7 @@ int tfhe_mi355_bootstrap_key_convert_async(TfheMi355Context *ctx, const uint64_t
                                            void *stream) {
     return guarded([&] {
         if (!ctx || !d_bsk) fail("null argument");
+        refuse_capture("tfhe_mi355_bootstrap_key_convert_async", (hipStream_t)stream);
         if (ctx->multi())  // d_bsk on the first device
             return multi_key_upload(ctx, KeyPart::Fourier, [&](TfheMi355Context *s) {
                 return tfhe_mi355_bootstrap_key_convert_async(s, d_bsk, len, stream);
@@ -2066,6 +2076,7 @@ int tfhe_mi355_keyswitch_key_upload_async(TfheMi355Context *ctx, const uint64_t 
                                           void *stream) {
     return guarded([&] {
         if (!ctx || !d_ksk) fail("null argument");
+        refuse_capture("tfhe_mi355_keyswitch_key_upload_async", (hipStream_t)stream);
         if (ctx->multi())  // d_ksk on the first device
             return multi_key_upload(ctx, KeyPart::Ksk, [&](TfheMi355Context *s) {
                 return tfhe_mi355_keyswitch_key_upload_async(s, d_ksk, len, stream);

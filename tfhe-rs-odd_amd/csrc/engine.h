@@ -20,6 +20,14 @@ namespace tfhe_mi355 {
 // buffer, ready flag) is seen by coalesced batches only as a whole.
 std::shared_ptr<void> begin_key_transaction(TfheMi355Context *ctx);
 
+// True while `s` is being captured into a graph, and when its capture state cannot be read: what must not
+// run under capture (event timing, a stream wait, a key upload) is then left out or refused.  The query
+// itself is legal under capture and enqueues nothing.
+inline bool stream_is_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone;
+}
+
 // Per-kernel durations measured on the launch stream (a profiling aid, off unless enabled through
 // tfhe_mi355_kernel_timing_enable): the launchers bracket every `every`-th launch of a kernel
 // family with HIP events; collect() waits for them and accumulates per-name totals.  bench.py
@@ -40,8 +48,7 @@ struct KernelTimer {
     // true when this launch of `name` is to be timed
     bool want(const char *name, hipStream_t s) {
         if (every <= 0) return false;
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return false;
+        if (stream_is_capturing(s)) return false;
         std::lock_guard<std::mutex> g(mu);
         return calls[name]++ % (uint64_t)every == 0;
     }
@@ -267,6 +274,14 @@ hipError_t launch_wop_sub_rows(uint64_t *cur, const uint64_t *x, size_t rows, si
                                hipStream_t s);
 hipError_t launch_wop_fill_luts(uint64_t *luts, size_t nluts, size_t glwe, size_t body_off, int first, int step,
                                 uint32_t *lut_indexes, size_t rows, hipStream_t s);
+
+// words[0, n) = 0 on the stream (lwe_ops.hip).  The launchers reset their ticket and flag words in the
+// caller's scratch with this kernel and not with hipMemsetAsync: captured into a hipGraph, the memset node
+// zeroes all its words on the first replay only (tests/test_async_graph_gpu.py, classic-1024-pbs-1100: the
+// second replay found its ticket as the previous contents of the scratch left it; a bare memset -> kernel
+// graph shows the same on an MI355X: of 4 bytes none, of 1792 and of 65536 bytes three quarters are zeroed
+// from the second replay on), while kernel nodes run in stream order on every replay.
+hipError_t launch_zero_words(uint32_t *words, size_t n, hipStream_t s);
 
 // batched LWE linear algebra / trivial PBS (lwe_ops.hip)
 hipError_t launch_torus_from_fraction(const double *fr, uint64_t *acc, uint64_t *set, size_t n, hipStream_t s);

@@ -39,6 +39,12 @@ __global__ void __launch_bounds__(256) trivial_pbs_kernel(uint64_t *__restrict__
     body[r * stride] = value >= modulus_sup ? 0 - entry : entry;
 }
 
+// words[0, n) = 0: the reset of a launcher's ticket and flag words (engine.h launch_zero_words)
+__global__ void __launch_bounds__(256) zero_words_kernel(uint32_t *__restrict__ words, size_t n) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < n) words[e] = 0;
+}
+
 // Diagnostic: the PBS kernels' backward torus conversion (fft_device.h frac_to_torus) applied to
 // given fractions: acc[i] += X(fr[i]) and set[i] = X(fr[i]), X = rint(fr * 2^64) mod 2^64.
 __global__ void __launch_bounds__(256) torus_from_fraction_kernel(const double *__restrict__ fr,
@@ -130,6 +136,13 @@ hipError_t launch_wop_fill_luts(uint64_t *luts, size_t nluts, size_t glwe, size_
     const size_t n = std::max(nluts * glwe, lut_indexes ? rows : 0);
     hipLaunchKernelGGL(wop_fill_luts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, luts, nluts, glwe,
                        body_off, first, step, lut_indexes, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_zero_words(uint32_t *words, size_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n > ((size_t)1 << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, words, n);
     return hipGetLastError();
 }
 

@@ -2609,7 +2609,8 @@ static hipError_t launch_quad(const LargePbsLaunch &a0, hipStream_t s) {
     if (!capturing && last[dev]) (void)hipStreamWaitEvent(s, last[dev], 0);
     for (int c0 = 0; c0 < a0.count; c0 += pass) {
         const int cnt = std::min(pass, a0.count - c0);
-        hipError_t e = hipMemsetAsync(a0.scratch, 0, (size_t)cnt * Cfg::R * Cfg::FLAG_BYTES, s);  // the flags
+        // the flags (a kernel, not a memset: engine.h launch_zero_words)
+        hipError_t e = launch_zero_words(static_cast<uint32_t *>(a0.scratch), (size_t)cnt * Cfg::R * Cfg::FLAG_BYTES / 4, s);
         if (e != hipSuccess) return e;
         TimedLaunch tl(a0.timer, "quad_cmux_kernel", s);
         const dim3 grid((unsigned)((cnt + 7) / 8) * 8 * Cfg::R), block(Cfg::THREADS);
