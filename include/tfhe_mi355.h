@@ -683,6 +683,35 @@ int tfhe_mi355_programmable_bootstrap_keyswitch_scratch(TfheMi355Context *ctx, s
  * device-resident radix ciphertexts. */
 int tfhe_mi355_lwe_scalar_mul_add_async(TfheMi355Context *ctx, uint64_t *d_y, const uint64_t *d_x, uint64_t scalar,
                                         size_t rows, size_t words, size_t y_stride, size_t x_stride, void *stream);
+/* One layer of block arithmetic in one call.  A radix operation alternates batched PBS layers with LWE linear
+ * algebra on single blocks: pack two blocks, subtract, negate with a correcting term, add a plaintext to the
+ * body (integer/server_key/comparator.rs:182-220, radix/neg.rs:56-73, shortint bivariate_pbs.rs:167-182).  An
+ * op describes one destination block as a sum of up to TFHE_MI355_BLOCK_OP_TERMS scaled source blocks; for
+ * every op, every row r < rows and every word w < words
+ *   dst[r][w] = sum over the present terms of scalar * src[r][w] + (w == words - 1 ? body_add : 0)
+ * wrapping mod 2^64, rows `stride` words apart (device pointers, 8-byte aligned).  A term with src == NULL is
+ * absent; an op with no term at all writes trivial ciphertexts (zero mask, body = body_add).
+ * Aliasing: a term may BE the destination (the same pointer and the same stride: the op then works in place).
+ * Any other overlap between a destination and a source or another destination of the same call is the caller's
+ * error: the ops of a call run in no defined order, and the result is then undefined.
+ * `ops` is host memory and is read before the call returns (the table travels in the kernel arguments, about
+ * 32 ops per launch; longer lists take several launches on the stream).  The call needs no scratch, does not
+ * allocate, synchronise or copy, and can be captured into a hipGraph, which then holds the table.
+ * Refused (rc 1): a NULL dst, a stride below `words`, words == 0 with n_ops > 0.  n_ops == 0 or rows == 0
+ * succeeds without a launch. */
+#define TFHE_MI355_BLOCK_OP_TERMS 4
+typedef struct {
+    uint64_t *dst;
+    uint64_t dst_stride; /* row r of the block at dst + r * dst_stride (words) */
+    uint64_t body_add;   /* added to the last word of every row */
+    struct {
+        const uint64_t *src;
+        uint64_t stride;
+        uint64_t scalar;
+    } term[TFHE_MI355_BLOCK_OP_TERMS]; /* src == NULL: term absent */
+} TfheMi355BlockOp;
+int tfhe_mi355_lwe_block_layer_async(TfheMi355Context *ctx, const TfheMi355BlockOp *ops, size_t n_ops,
+                                     size_t rows, size_t words, void *stream);
 /* trivial_pbs_assign (shortint/server_key/mod.rs:763-781) on the bodies of `rows` trivial
  * ciphertexts (d_body points at the first body, rows `stride` words apart) with the GLWE
  * accumulator d_lut ((k+1)*N words, device). */

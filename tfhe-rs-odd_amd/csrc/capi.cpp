@@ -3193,6 +3193,34 @@ int tfhe_mi355_lwe_scalar_mul_add_async(TfheMi355Context *ctx, uint64_t *d_y, co
     });
 }
 
+static_assert(sizeof(TfheMi355BlockOp) == sizeof(BlockLayerOp) && TFHE_MI355_BLOCK_OP_TERMS == BLOCK_LAYER_TERMS &&
+                  offsetof(TfheMi355BlockOp, body_add) == offsetof(BlockLayerOp, body_add) &&
+                  offsetof(TfheMi355BlockOp, term) == offsetof(BlockLayerOp, term) &&
+                  sizeof(((TfheMi355BlockOp *)0)->term[0]) == sizeof(((BlockLayerOp *)0)->term[0]),
+              "TfheMi355BlockOp and the launcher's BlockLayerOp are one layout");
+
+int tfhe_mi355_lwe_block_layer_async(TfheMi355Context *ctx, const TfheMi355BlockOp *ops, size_t n_ops, size_t rows,
+                                     size_t words, void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!ops && n_ops)) fail("null argument");
+        if (n_ops && words == 0) fail("block layer: rows of zero words");
+        for (size_t i = 0; i < n_ops; i++) {
+            if (!ops[i].dst) fail("block layer: op %zu has a null destination", i);
+            if (ops[i].dst_stride < words)
+                fail("block layer: op %zu: destination row stride smaller than the row", i);
+            for (int t = 0; t < TFHE_MI355_BLOCK_OP_TERMS; t++)
+                if (ops[i].term[t].src && ops[i].term[t].stride < words)
+                    fail("block layer: op %zu term %d: row stride smaller than the row", i, t);
+        }
+        if (n_ops == 0 || rows == 0) return;
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        check(launch_lwe_block_layer(reinterpret_cast<const BlockLayerOp *>(ops), n_ops, rows, words,
+                                     (hipStream_t)stream),
+              "lwe block layer");
+    });
+}
+
 int tfhe_mi355_trivial_pbs_async(TfheMi355Context *ctx, uint64_t *d_body, size_t rows, size_t stride,
                                  const uint64_t *d_lut, void *stream) {
     return guarded([&] {

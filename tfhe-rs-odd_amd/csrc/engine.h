@@ -290,6 +290,26 @@ hipError_t launch_lwe_scalar_mul_add(uint64_t *y, const uint64_t *x, uint64_t sc
 hipError_t launch_trivial_pbs(uint64_t *body, size_t rows, size_t stride, const uint64_t *lut_body, uint64_t delta,
                               uint64_t modulus_sup, uint64_t box, hipStream_t s);
 
+// One layer of block arithmetic (lwe_ops.hip lwe_block_layer_kernel): for every op, r < rows, w < words
+//   dst[r][w] = sum_t scalar_t * src_t[r][w] + (w == words - 1 ? body_add : 0)   (wrapping; src == nullptr: absent).
+// The layout is TfheMi355BlockOp's (include/tfhe_mi355.h; capi.cpp asserts it).  `ops` is host memory, copied
+// into the kernel arguments before the call returns: BLOCK_LAYER_OPS_PER_LAUNCH entries of 120 bytes stay under
+// the 4 KiB of kernel arguments, longer lists take several launches.  No allocation, no copy, no wait.
+constexpr int BLOCK_LAYER_TERMS = 4;
+constexpr int BLOCK_LAYER_OPS_PER_LAUNCH = 32;
+constexpr size_t BLOCK_LAYER_MAX_WORKGROUPS = 2048;
+struct BlockLayerOp {
+    uint64_t *dst;
+    uint64_t dst_stride;
+    uint64_t body_add;
+    struct {
+        const uint64_t *src;
+        uint64_t stride;
+        uint64_t scalar;
+    } term[BLOCK_LAYER_TERMS];
+};
+hipError_t launch_lwe_block_layer(const BlockLayerOp *ops, size_t n_ops, size_t rows, size_t words, hipStream_t s);
+
 // GLWE x plaintext-polynomial products (glwe_ops.hip):
 //   out[c][i] = sum_{j<J} glwe_in[c][j] * polys[i][j]   in (Z/2^64)[X]/(X^N+1), per GLWE polynomial,
 // optionally sample-extracted at degree 0.  Serves the fork's MVB products v0 * v_i

@@ -9,6 +9,7 @@
 //   trivial_pbs_assign     (shortint/server_key/mod.rs:763-781)
 // All arithmetic is wrapping mod 2^64, as the reference's.
 #include <algorithm>
+#include <cstring>
 
 #include "engine.h"
 #include "fft_device.h"
@@ -25,6 +26,35 @@ __global__ void __launch_bounds__(256) lwe_scalar_mul_add_kernel(uint64_t *__res
     uint64_t v = y[r * y_stride + w] * scalar;
     if (x) v += x[r * x_stride + w];
     y[r * y_stride + w] = v;
+}
+
+// One layer of block arithmetic in one launch: for the op of blockIdx.y, every row r < rows and word w < words,
+//   dst[r][w] = sum over the present terms of scalar_t * src_t[r][w] + (w == words - 1 ? body_add : 0).
+// Replaces, for a whole layer of a radix DAG at once, the packing / subtraction / negation with its correcting
+// term that the reference runs block by block between two PBS layers (pack_block_chunk, compare_block_assign:
+// integer/server_key/comparator.rs:182-220; unchecked_neg_assign: radix/neg.rs:56-73) and the copies around the
+// batched PBS.  The table travels by value in the kernel arguments and is indexed by blockIdx.y alone, so an
+// entry is read with scalar loads; lanes run along w (8-byte accesses, 512 B per wave: rows are only 8-byte
+// aligned, lwe_size being odd).  Tiles of 256 words are handed out grid-stride over (row, tile of the row); a
+// term that is the destination itself (same pointer, same stride) is read and written by the same lane.
+struct BlockLayerTable {
+    BlockLayerOp op[BLOCK_LAYER_OPS_PER_LAUNCH];
+};
+
+__global__ void __launch_bounds__(256) lwe_block_layer_kernel(const BlockLayerTable table, uint32_t rows, uint32_t words,
+                                                              uint32_t tiles_per_row) {
+    const BlockLayerOp &op = table.op[blockIdx.y];
+    const uint32_t tiles = rows * tiles_per_row;
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint32_t r = t / tiles_per_row;
+        const uint32_t w = (t - r * tiles_per_row) * 256 + threadIdx.x;
+        if (w >= words) continue;
+        uint64_t v = w + 1 == words ? op.body_add : 0;
+#pragma unroll
+        for (int i = 0; i < BLOCK_LAYER_TERMS; i++)
+            if (op.term[i].src) v += op.term[i].scalar * op.term[i].src[(size_t)r * op.term[i].stride + w];
+        op.dst[(size_t)r * op.dst_stride + w] = v;
+    }
 }
 
 // trivial ciphertexts (zero mask): body <- LUT body at the box of body / delta (negated past the
@@ -159,6 +189,27 @@ hipError_t launch_lwe_scalar_mul_add(uint64_t *y, const uint64_t *x, uint64_t sc
     hipLaunchKernelGGL(lwe_scalar_mul_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, x, scalar,
                        rows, words, y_stride, x_stride);
     return hipGetLastError();
+}
+
+hipError_t launch_lwe_block_layer(const BlockLayerOp *ops, size_t n_ops, size_t rows, size_t words, hipStream_t s) {
+    if (n_ops == 0 || rows == 0 || words == 0) return hipSuccess;
+    const size_t tiles_per_row = (words + 255) / 256;
+    if (words > 0xFFFFFFFFull || rows > 0xFFFFFFFFull / tiles_per_row) return hipErrorInvalidValue;
+    const size_t tiles = rows * tiles_per_row;
+    // lists longer than one table: several launches, in stream order
+    for (size_t first = 0; first < n_ops; first += BLOCK_LAYER_OPS_PER_LAUNCH) {
+        const size_t n = std::min(n_ops - first, (size_t)BLOCK_LAYER_OPS_PER_LAUNCH);
+        BlockLayerTable table;
+        std::memset(&table, 0, sizeof table);
+        std::memcpy(table.op, ops + first, n * sizeof(BlockLayerOp));
+        // about eight workgroups per compute unit over the whole launch; the grid-stride loop takes the rest
+        const size_t per_op = std::max((size_t)1, BLOCK_LAYER_MAX_WORKGROUPS / n);
+        hipLaunchKernelGGL(lwe_block_layer_kernel, dim3((unsigned)std::min(tiles, per_op), (unsigned)n), dim3(256), 0, s,
+                           table, (uint32_t)rows, (uint32_t)words, (uint32_t)tiles_per_row);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_trivial_pbs(uint64_t *body, size_t rows, size_t stride, const uint64_t *lut_body, uint64_t delta,

@@ -58,6 +58,24 @@ class TfheMi355LweSource(ctypes.Structure):
     ]
 
 
+BLOCK_OP_TERMS = 4
+
+
+class TfheMi355BlockOpTerm(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("stride", ctypes.c_uint64), ("scalar", ctypes.c_uint64)]
+
+
+class TfheMi355BlockOp(ctypes.Structure):
+    """dst rows = sum of scalar * src rows + body_add on the last word (device pointers, strides in words;
+    src NULL: term absent)."""
+    _fields_ = [
+        ("dst", ctypes.c_void_p),
+        ("dst_stride", ctypes.c_uint64),
+        ("body_add", ctypes.c_uint64),
+        ("term", TfheMi355BlockOpTerm * BLOCK_OP_TERMS),
+    ]
+
+
 class TfheMi355CiphertextInfo(ctypes.Structure):
     _fields_ = [
         ("lwe_dimension", ctypes.c_uint32),
@@ -128,6 +146,8 @@ SIGNATURES = [
      [vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
     ("tfhe_mi355_lwe_scalar_mul_add_async", ctypes.c_int,
      [vp, vp, vp, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp]),
+    ("tfhe_mi355_lwe_block_layer_async", ctypes.c_int,
+     [vp, ctypes.POINTER(TfheMi355BlockOp), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp]),
     ("tfhe_mi355_trivial_pbs_async", ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp]),
     ("tfhe_mi355_client_gen_multi_bit_bootstrap_key", ctypes.c_int,
      [ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,

@@ -1010,6 +1010,28 @@ class Engine:
         _lib.call("tfhe_mi355_lwe_scalar_mul_add_async", self._h, y_ptr, x_ptr, scalar % (1 << 64), rows, words,
                   y_stride, x_stride, _stream_ptr(stream))
 
+    @staticmethod
+    def block_ops(ops):
+        """The C table of a block layer from [(dst_ptr, dst_stride, body_add, [(src_ptr, stride, scalar), ...])]
+        (raw device pointers, strides in words, at most 4 terms per op).  A table can be kept and passed to
+        lwe_block_layer_async again."""
+        table = (_lib.TfheMi355BlockOp * max(len(ops), 1))()
+        for o, (dst, dst_stride, body_add, terms) in zip(table, ops):
+            if len(terms) > _lib.BLOCK_OP_TERMS:
+                raise ValueError(f"a block op takes at most {_lib.BLOCK_OP_TERMS} terms, got {len(terms)}")
+            o.dst, o.dst_stride, o.body_add = dst, dst_stride, body_add % (1 << 64)
+            for t, (src, stride, scalar) in zip(o.term, terms):
+                t.src, t.stride, t.scalar = src, stride, scalar % (1 << 64)
+        return table, len(ops)
+
+    def lwe_block_layer_async(self, ops, rows: int, words: int, stream=None) -> None:
+        """One layer of block arithmetic in one launch: for every op, dst[r] = sum_t scalar_t * src_t[r] with
+        body_add on the last word (u64 wrapping), r < rows, `words` words per row.  `ops` is a list as block_ops
+        takes it, or what block_ops returned.  A term may be the destination itself (same pointer and stride);
+        any other overlap with a destination is the caller's error."""
+        table, n = ops if isinstance(ops, tuple) else self.block_ops(ops)
+        _lib.call("tfhe_mi355_lwe_block_layer_async", self._h, table, n, rows, words, _stream_ptr(stream))
+
     def trivial_pbs_async(self, body_ptr: int, rows: int, stride: int, d_lut, stream=None) -> None:
         _lib.call("tfhe_mi355_trivial_pbs_async", self._h, body_ptr, rows, stride, _dev_ptr(d_lut),
                   _stream_ptr(stream))

@@ -15,6 +15,9 @@ operand pairs at once:
   full_propagate_parallelized / partial_propagate_parallelized
                                                             radix_parallel/mod.rs:88-155
   ServerKey.blockshift                                      radix/scalar_mul.rs:345-355
+  ServerKey neg, sub, bitand / bitor / bitxor / bitnot, eq / ne, gt / ge / lt / le, if_then_else / cmux, min / max
+  (unchecked and default forms, unsigned)                   radix/neg.rs, radix_parallel/{neg,sub,bitwise_op,comparison,
+                                                            cmux}.rs, comparator.rs: see "neg, sub, ..." in ServerKey
   shortint unchecked_apply_lookup_table_bivariate_assign    shortint/server_key/bivariate_pbs.rs:69-182
   WopbsKey (wopbs, wopbs_without_padding, bivariate_wopbs_with_degree, generate_lut_radix,
   generate_lut_radix_without_padding, generate_lut_bivariate_radix, keyswitch_to_wopbs_params,
@@ -81,19 +84,76 @@ class RadixBatch:
 
 
 class _PbsLayer:
-    """Collects the independent LUT applications of one DAG layer and runs them in one launch."""
+    """Collects the independent LUT applications of one DAG layer and runs them in one launch.
+
+    A request may carry a prepare op: the PBS input is then not block j of the batch as it stands but
+        sum over terms of scalar * block i of a source batch  +  body_add on the body,
+    the packing, subtraction or sum the reference does on the block right before the LUT, and the PBS output
+    lands in block j with post_add * delta added to its body (compare_block_assign's + 1).  A layer with such a
+    request runs fused (flush_fused): ONE block-layer call assembles the input rows of every request in the
+    layer's input buffer, the batched KS+PBS follows, ONE more block-layer call scatters the outputs to their
+    blocks.  Layers without one keep the launch path below, as the multiply DAG pins it."""
 
     def __init__(self, sk: "ServerKey"):
         self.sk = sk
-        self.reqs = []  # (batch, block, lut)
+        self.reqs = []  # (batch, block, lut), or with a prepare op (batch, block, lut, body_add, terms, post_add)
 
-    def add(self, rb: RadixBatch, j: int, lut: LookupTable):
-        self.reqs.append((rb, j, lut))
+    def add(self, rb: RadixBatch, j: int, lut: LookupTable, prepare=None, post_add: int = 0):
+        """prepare: (body_add, [(source batch, block, scalar), ...]); None with post_add = 0: block j as it is"""
+        if prepare is None and not post_add:
+            self.reqs.append((rb, j, lut))
+        else:
+            body_add, terms = prepare if prepare is not None else (0, [(rb, j, 1)])
+            self.reqs.append((rb, j, lut, body_add, list(terms), post_add))
+
+    def flush_fused(self, reqs):
+        """The layer with prepare ops.  Request q of the non-trivial ones owns rows [qK, (q+1)K) of the input
+        buffer.  A request whose sources are all trivial (or that has none) is a trivial ciphertext: its op
+        writes block j itself, the trivial PBS follows on the block and it stays NOISE_ZERO."""
+        sk, ops = self.sk, self.sk.ops
+        reqs = [r if len(r) == 6 else (r[0], r[1], r[2], 0, [(r[0], r[1], 1)], 0) for r in reqs]
+        K, size, delta = reqs[0][0].count, sk.lwe_size, sk.p.delta
+        todo, triv, luts, lut_of = [], [], [], {}
+        for req in reqs:
+            if all(src.is_trivial_block(i) for src, i, _ in req[4]):
+                triv.append(req)
+                continue
+            if id(req[2]) not in lut_of:
+                lut_of[id(req[2])] = len(luts)
+                luts.append(req[2])
+            todo.append(req)
+        x = ops.rows(len(todo) * K, size) if todo else None
+        pre = [(x[q * K:(q + 1) * K], body_add, [(ops.block(src, i), s) for src, i, s in terms])
+               for q, (_, _, _, body_add, terms, _) in enumerate(todo)]
+        pre += [(ops.block(rb, j), body_add, [(ops.block(src, i), s) for src, i, s in terms])
+                for rb, j, _, body_add, terms, _ in triv]
+        ops.block_layer(pre)
+        post = []
+        for rb, j, lut, _, _, post_add in triv:
+            ops.trivial_pbs(rb, j, lut)
+            if post_add:
+                post.append((ops.block(rb, j), post_add * delta, [(ops.block(rb, j), 1)]))
+        if todo:
+            out = ops.pbs_buffer(x, K, [lut_of[id(r[2])] for r in todo], luts)
+            sk.pbs_count += len(todo) * K
+            sk.launches += 1
+            post += [(ops.block(rb, j), post_add * delta, [(out[q * K:(q + 1) * K], 1)])
+                     for q, (rb, j, _, _, _, post_add) in enumerate(todo)]
+        if post:
+            ops.block_layer(post)
+        for rb, j, lut, _, _, post_add in reqs:
+            rb.degree[j] = lut.degree + post_add
+        for rb, j, _, _, _, _ in todo:
+            rb.noise[j] = NOISE_NOMINAL
+        for rb, j, _, _, _, _ in triv:
+            rb.noise[j] = NOISE_ZERO
 
     def flush(self):
         reqs, self.reqs = self.reqs, []
         if not reqs:
             return
+        if any(len(r) == 6 for r in reqs):
+            return self.flush_fused(reqs)
         sk = self.sk
         todo, luts, lut_of = [], [], {}
         for rb, j, lut in reqs:
@@ -166,6 +226,28 @@ class _HostOps:
         neg = value >= np.uint64(modulus_sup)
         entry = body[((value % np.uint64(modulus_sup)) * np.uint64(box)).astype(np.int64)]
         rb.data[:, j, -1] = np.where(neg, np.uint64(0) - entry, entry)
+
+    def rows(self, n, s):
+        return np.empty((n, s), dtype=np.uint64)
+
+    def block(self, rb, j):
+        return rb.data[:, j, :]
+
+    def block_layer(self, ops):
+        """The block layer's formula, the reference of the device kernel (lwe_block_layer_kernel): for every
+        op (dst, body_add, [(src, scalar), ...]) over [K, words] views,
+            dst[r][w] = sum_t scalar_t * src_t[r][w] + (w == words - 1 ? body_add : 0)   wrapping mod 2^64.
+        A source may be the destination itself; nothing else may overlap a destination."""
+        for dst, body_add, terms in ops:
+            acc = np.zeros(dst.shape, dtype=np.uint64)
+            for src, scalar in terms:
+                acc += np.uint64(scalar % (1 << 64)) * src
+            acc[:, -1] += np.uint64(body_add % (1 << 64))
+            dst[...] = acc
+
+    def pbs_buffer(self, x, K, lut_of_request, luts):
+        idx = np.repeat(np.asarray(lut_of_request, dtype=np.uint32), K)
+        return self.sk.shortint.engine_ks_pbs(x, np.stack([lut.acc for lut in luts]), idx if len(luts) > 1 else None)
 
     def pbs_rows(self, todo, luts):
         K = todo[0][0].count
@@ -276,34 +358,72 @@ class _DeviceOps:
         seen: the DAG repeats the same layers for every multiply, so a steady-state multiply does
         no host-to-device copy (nothing stalls the stream between launches, and the whole DAG can
         be captured into one hipGraph)."""
-        K = todo[0][0].count
-        key = (K, tuple(id(lut) for lut in luts), tuple(li for _, _, li in todo) if len(luts) > 1 else ())
+        return self._tables(todo[0][0].count, [li for _, _, li in todo], luts)
+
+    def _tables(self, K, lut_of_request, luts):
+        key =(K, tuple(id(lut) for lut in luts), tuple(lut_of_request) if len(luts) > 1 else ())
         hit = self._stacks.get(key)
         if hit is None or any(a is not b for a, b in zip(hit[0], luts)):
             d_luts = self.from_host(np.stack([lut.acc for lut in luts]))
             idx = None
             if len(luts) > 1:
-                li = np.repeat(np.asarray([li for _, _, li in todo], dtype=np.int32), K)
+                li = np.repeat(np.asarray(lut_of_request, dtype=np.int32), K)
                 idx = self.torch.from_numpy(li).to(self.device)
             hit = (list(luts), d_luts, idx)
             self._stacks.put(key, hit)
         return hit[1], hit[2]
 
-    def pbs_rows(self, todo, luts):
+    def rows(self, n, s):
+        return self.torch.empty((n, s), dtype=self.torch.int64, device=self.device)
+
+    def block(self, rb, j):
+        return rb.data[:, j, :]
+
+    TERMS = 4  # TFHE_MI355_BLOCK_OP_TERMS
+
+    def block_layer(self, ops):
+        """_HostOps.block_layer on the device: one lwe_block_layer_async call (one launch up to 32 ops).  An op
+        with more than 4 terms (the sums of eq / ne over up to msg * carry - 1 blocks) goes on in place in a
+        further call per 3 terms, after the first: calls on one stream run in order, the ops of one call do not."""
+        if not ops:
+            return
+        rows, words = ops[0][0].shape
+        more = ops
+        first = True
+        while more:
+            table, rest = [], []
+            for dst, body_add, terms in more:
+                assert dst.shape == (rows, words) and dst.stride(1) == 1
+                head = terms[:self.TERMS] if first else [(dst, 1)] + terms[:self.TERMS - 1]
+                tail = terms[self.TERMS:] if first else terms[self.TERMS - 1:]
+                table.append((dst.data_ptr(), dst.stride(0), body_add if first else 0,
+                              [(src.data_ptr(), src.stride(0), scalar) for src, scalar in head]))
+                if tail:
+                    rest.append((dst, 0, tail))
+            self.eng.lwe_block_layer_async(table, rows, words)
+            more, first = rest, False
+
+    def pbs_buffer(self, x, K, lut_of_request, luts):
+        """batched KS+PBS of the rows of x (request q: rows [qK, (q+1)K), LUT lut_of_request[q]) -> new rows"""
         torch = self.torch
-        K = todo[0][0].count
-        x = torch.cat([rb.data[:, j, :] for rb, j, _ in todo], dim=0)
         n = x.shape[0]
-        d_luts, idx = self._layer_tables(todo, luts)
+        d_luts, idx = self._tables(K, lut_of_request, luts)
         out = torch.empty_like(x)
         need = self.eng.ks_pbs_scratch_bytes(n)
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         self.eng.keyswitch_programmable_bootstrap_async(x, out, d_luts, len(luts), n, self._scratch,
                                                         d_lut_indexes=idx)
+        return out
+
+    def pbs_rows(self, todo, luts):
+        torch = self.torch
+        K = todo[0][0].count
+        x = torch.cat([rb.data[:, j, :] for rb, j, _ in todo], dim=0)
+        out = self.pbs_buffer(x, K, [li for _, _, li in todo], luts)
         for q, (rb, j, _) in enumerate(todo):
             rb.data[:, j, :].copy_(out[q * K:(q + 1) * K])
-        return n
+        return x.shape[0]
 
 
 def propagation_refusal(msg: int, carry: int):
@@ -342,6 +462,39 @@ def mul_refusal(msg: int, carry: int):
     return None
 
 
+def bivariate_refusal(msg: int, carry: int):
+    """Why a bivariate PBS layer (bitand / bitor / bitxor, eq / ne, zero_out_if of the cmux) cannot serve a pair:
+    the operands are packed lhs * message_modulus + rhs into one block (bivariate_pbs.rs:167-182)."""
+    if carry < msg:
+        return "carry_modulus < message_modulus: two messages packed for a bivariate PBS overflow the block"
+    return None
+
+
+def comparison_refusal(msg: int, carry: int):
+    """Comparator::new (comparator.rs:52-56)."""
+    if msg * carry < 16:
+        return "message_modulus * carry_modulus < 16: at least 4 bits of space (message + carry) are required to compare"
+    return None
+
+
+IS_INFERIOR, IS_EQUAL, IS_SUPERIOR = 0, 1, 2   # comparator.rs:43-45
+_NEG1 = (1 << 64) - 1
+
+
+def _after_bitand(a: int, b: int) -> int:    # shortint/ciphertext/mod.rs:195-197
+    return min(a, b)
+
+
+def _after_bitor(a: int, b: int) -> int:     # :181-193
+    hi, lo = max(a, b), min(a, b)
+    return max(hi | i for i in range(lo + 1))
+
+
+def _after_bitxor(a: int, b: int) -> int:    # :166-179
+    hi, lo = max(a, b), min(a, b)
+    return max([hi] + [hi ^ i for i in range(lo + 1)])
+
+
 class ServerKey:
     """integer ServerKey (integer/server_key/mod.rs) over a shortint ServerKey with the GPU engine."""
 
@@ -371,6 +524,9 @@ class ServerKey:
             lambda msb, lsb: lsb if msb == OUTPUT_CARRY_PROPAGATED else msb)
         self.propagation_refusal = propagation_refusal(m, self.carry)
         self.mul_refusal = self.propagation_refusal or mul_refusal(m, self.carry)
+        self.bivariate_refusal = bivariate_refusal(m, self.carry)
+        self.comparison_refusal = comparison_refusal(m, self.carry)
+        self._luts = {}   # the LUTs of neg .. min / max, built on first use: (name, ...) -> LookupTable
 
     def _require(self, op: str, refusal):
         """The carry-propagating entry points refuse a parameter set they cannot serve before the
@@ -627,6 +783,351 @@ class ServerKey:
         if not lhs.block_carries_are_empty(self.msg):
             self.full_propagate(lhs)
         return self.unchecked_mul(lhs, rhs)
+
+    # ---- neg, sub, bitwise ops, comparisons, cmux, min / max ----------------------------------------------
+    # Mirrors of the reference functions named in each docstring, for K unsigned operands at once.  Every PBS
+    # layer is a fused _PbsLayer (flush_fused): the block arithmetic the reference does between two layers --
+    # pack_block_chunk, the LWE subtraction of compare_block_assign, 4 * high + low of the sign tree, the sums
+    # of eq / ne, the bivariate packing -- is the prepare op of the request that consumes it.  A BooleanBlock
+    # is a one-block RadixBatch of degree <= 1.  Out of scope: signed integers, scalar operands, overflowing
+    # sub, shifts / rotations / div / abs and the smart_* forms.
+    def _lut(self, key, f, bivariate: bool = False) -> LookupTable:
+        """One LookupTable object per function for the life of the key: the device caches go by identity."""
+        t = self._luts.get(key)
+        if t is None:
+            t = self.generate_lookup_table_bivariate(f) if bivariate else self.shortint.generate_lookup_table(f)
+            self._luts[key] = t
+        return t
+
+    def _new(self, count: int, num_blocks: int) -> RadixBatch:
+        """a batch whose blocks are all written before they are read"""
+        return RadixBatch(self.ops.rows(count * num_blocks, self.lwe_size).reshape(count, num_blocks, self.lwe_size),
+                          [0] * num_blocks, [NOISE_ZERO] * num_blocks)
+
+    def _clean(self, ct: RadixBatch) -> RadixBatch:
+        """the operand itself with empty carries, or a propagated clone (the default forms' preamble)"""
+        ct = self._resident(ct)
+        if ct.block_carries_are_empty(self.msg):
+            return ct
+        ct = ct.clone()
+        self.full_propagate(ct)
+        return ct
+
+    def unchecked_neg(self, ct: RadixBatch) -> RadixBatch:
+        """unchecked_neg / unchecked_neg_assign (radix/neg.rs:39-73) over shortint
+        unchecked_neg_assign_with_correcting_term (shortint/server_key/neg.rs:223-246): block j becomes
+        (z - z_b) * delta - block, z = max(ceil((degree + z_b) / msg), 1) * msg, z_b the carry of the correcting
+        term of the block before.  One block op per block, no PBS."""
+        ct = self._resident(ct)
+        res = self._new(ct.count, ct.num_blocks)
+        ops, z_b = [], 0
+        for j in range(ct.num_blocks):
+            degree = ct.degree[j] + z_b                        # unchecked_scalar_add_assign(block, z_b)
+            z = max(-(-degree // self.msg), 1) * self.msg
+            ops.append((self.ops.block(res, j), (z - z_b) * self.p.delta, [(self.ops.block(ct, j), _NEG1)]))
+            res.degree[j] = z - z_b
+            res.noise[j] = ct.noise[j]
+            z_b = z // self.msg
+        self.ops.block_layer(ops)
+        return res
+
+    def neg_parallelized(self, ct: RadixBatch) -> RadixBatch:
+        """radix_parallel/neg.rs:77-100 (the branch of is_eligible_for_parallel_single_carry_propagation)."""
+        self._require("neg_parallelized", self.propagation_refusal)
+        res = self.unchecked_neg(self._clean(ct))
+        self._propagate_single_carry_low_latency(res)
+        return res
+
+    def unchecked_sub_assign(self, lhs: RadixBatch, rhs: RadixBatch):
+        """radix/sub.rs:80-86."""
+        self.unchecked_add_assign(lhs, self.unchecked_neg(rhs))
+
+    def sub_assign_parallelized(self, lhs: RadixBatch, rhs: RadixBatch):
+        """radix_parallel/sub.rs:206-243, the eligible branch: unchecked_neg, then
+        unchecked_add_assign_parallelized_low_latency.  lhs must be resident (it is assigned)."""
+        self._require("sub_assign_parallelized", self.propagation_refusal)
+        rhs = self._clean(rhs)
+        if not lhs.block_carries_are_empty(self.msg):
+            self.full_propagate(lhs)
+        self._unchecked_add_assign_low_latency(lhs, self.unchecked_neg(rhs))
+
+    def sub_parallelized(self, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
+        """radix_parallel/sub.rs:162-169."""
+        self._require("sub_parallelized", self.propagation_refusal)
+        res = self._resident(lhs).clone()
+        self.sub_assign_parallelized(res, rhs)
+        return res
+
+    # -- bitwise --------------------------------------------------------------------------------------------
+    _BITOPS = {"bitand": (lambda x, y: x & y, _after_bitand), "bitor": (lambda x, y: x | y, _after_bitor),
+               "bitxor": (lambda x, y: x ^ y, _after_bitxor)}
+
+    def _unchecked_bitop_assign(self, name: str, lhs: RadixBatch, rhs: RadixBatch):
+        """unchecked_bit{and,or,xor}_assign_parallelized (radix_parallel/bitwise_op.rs:15-26, 180-191, 347-358)
+        over shortint unchecked_evaluate_bivariate_function_assign (bivariate_pbs.rs:277-290): per block
+        lhs * (rhs.degree + 1) + rhs, the LUT of that factor, then Degree::after_bit*.  One PBS layer."""
+        self._require(f"unchecked_{name}_assign_parallelized", self.bivariate_refusal)
+        f, after = self._BITOPS[name]
+        rhs = self._resident(rhs)
+        total, m = self.msg * self.carry, self.msg
+        layer = _PbsLayer(self)
+        degrees = []
+        for j in range(lhs.num_blocks):
+            factor = rhs.degree[j] + 1
+            if lhs.degree[j] * factor + rhs.degree[j] >= total:
+                raise ValueError(f"unchecked_{name}: block {j} (degrees {lhs.degree[j]}, {rhs.degree[j]}) cannot be "
+                                 "packed for a bivariate PBS")
+            lut = self._lut((name, factor), lambda x, f=f, k=factor: f((x // k) % m, (x % k) % m))
+            degrees.append(after(lhs.degree[j], rhs.degree[j]))
+            layer.add(lhs, j, lut, prepare=(0, [(lhs, j, factor), (rhs, j, 1)]))
+        layer.flush()
+        lhs.degree = degrees
+
+    def _bitop(self, name: str, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
+        """bit{and,or,xor}_parallelized (bitwise_op.rs:129-169, 296-336, 463-503)."""
+        self._require(f"{name}_parallelized", self.bivariate_refusal)
+        lhs, rhs = self._clean(lhs), self._clean(rhs)
+        res = lhs.clone()
+        self._unchecked_bitop_assign(name, res, rhs)
+        return res
+
+    def unchecked_bitand_assign_parallelized(self, lhs, rhs):
+        self._unchecked_bitop_assign("bitand", lhs, rhs)
+
+    def unchecked_bitor_assign_parallelized(self, lhs, rhs):
+        self._unchecked_bitop_assign("bitor", lhs, rhs)
+
+    def unchecked_bitxor_assign_parallelized(self, lhs, rhs):
+        self._unchecked_bitop_assign("bitxor", lhs, rhs)
+
+    def bitand_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._bitop("bitand", lhs, rhs)
+
+    def bitor_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._bitop("bitor", lhs, rhs)
+
+    def bitxor_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._bitop("bitxor", lhs, rhs)
+
+    def bitnot_parallelized(self, ct: RadixBatch) -> RadixBatch:
+        """bitwise_op.rs:540-562: (!x) % message_modulus on every block."""
+        res = self._resident(ct).clone()
+        if not res.block_carries_are_empty(self.msg):
+            self.full_propagate(res)
+        m = self.msg
+        lut = self._lut(("bitnot",), lambda x: (~x) % m)
+        layer = _PbsLayer(self)
+        for j in range(res.num_blocks):
+            layer.add(res, j, lut)
+        layer.flush()
+        return res
+
+    # -- eq / ne ----------------------------------------------------------------------------------------------
+    def _reduce_block_comparisons(self, blocks: list, all_true: bool) -> RadixBatch:
+        """are_all_comparisons_block_true (scalar_comparison.rs:147-191) and the reduction of
+        unchecked_ne_parallelized (comparison.rs:55-83): blocks of 0 / 1 are summed in chunks of
+        msg * carry - 1, a LUT tells whether the sum is the chunk's length (eq) or non-zero (ne); one PBS layer
+        per pass.  blocks: [(batch, block)]; returns the one-block batch."""
+        count = blocks[0][0].count
+        max_value = self.msg * self.carry - 1
+        while len(blocks) > 1:
+            chunks = [blocks[c:c + max_value] for c in range(0, len(blocks), max_value)]
+            out = self._new(count, len(chunks))
+            layer = _PbsLayer(self)
+            for c, chunk in enumerate(chunks):
+                n = len(chunk)
+                lut = self._lut(("sum_is", n), lambda x, n=n: int(x == n)) if all_true else \
+                    self._lut(("sum_non_zero",), lambda x: int(x != 0))
+                layer.add(out, c, lut, prepare=(0, [(rb, j, 1) for rb, j in chunk]))
+            layer.flush()
+            blocks = [(out, c) for c in range(len(chunks))]
+        rb, _ = blocks[0]
+        assert rb.num_blocks == 1   # one block in, or the single chunk of the last pass
+        return rb
+
+    def _unchecked_equality(self, name: str, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
+        self._require(f"unchecked_{name}_parallelized", self.bivariate_refusal)
+        lhs, rhs = self._resident(lhs), self._resident(rhs)
+        assert lhs.num_blocks == rhs.num_blocks and lhs.num_blocks > 0
+        eq = name == "eq"
+        lut = self._lut((name,), (lambda x, y: int(x == y)) if eq else (lambda x, y: int(x != y)), bivariate=True)
+        cmp = self._new(lhs.count, lhs.num_blocks)
+        layer = _PbsLayer(self)
+        for j in range(lhs.num_blocks):
+            assert rhs.degree[j] < self.msg and lhs.degree[j] < self.msg
+            layer.add(cmp, j, lut, prepare=(0, [(lhs, j, self.msg), (rhs, j, 1)]))
+        layer.flush()
+        return self._reduce_block_comparisons([(cmp, j) for j in range(cmp.num_blocks)], eq)
+
+    def unchecked_eq_parallelized(self, lhs, rhs) -> RadixBatch:
+        """radix_parallel/comparison.rs:10-33."""
+        return self._unchecked_equality("eq", lhs, rhs)
+
+    def unchecked_ne_parallelized(self, lhs, rhs) -> RadixBatch:
+        """radix_parallel/comparison.rs:35-83."""
+        return self._unchecked_equality("ne", lhs, rhs)
+
+    def eq_parallelized(self, lhs, rhs) -> RadixBatch:
+        """radix_parallel/comparison.rs:207-237."""
+        self._require("eq_parallelized", self.bivariate_refusal)
+        return self._unchecked_equality("eq", self._clean(lhs), self._clean(rhs))
+
+    def ne_parallelized(self, lhs, rhs) -> RadixBatch:
+        """radix_parallel/comparison.rs:239-269."""
+        self._require("ne_parallelized", self.bivariate_refusal)
+        return self._unchecked_equality("ne", self._clean(lhs), self._clean(rhs))
+
+    # -- order ------------------------------------------------------------------------------------------------
+    def _unchecked_compare(self, lhs: RadixBatch, rhs: RadixBatch):
+        """Comparator::unchecked_compare_parallelized (comparator.rs:389-463): the sign block (batch, block) of
+        lhs against rhs, IS_INFERIOR / IS_EQUAL / IS_SUPERIOR.  compare_block_assign (:193-220) is the true LWE
+        subtraction, sign_lut, + 1 on the body; with carry >= msg it runs on pairs of blocks packed by
+        pack_block_chunk (:182-187), so its PBS input is the one op  m * lhs_hi + lhs_lo - m * rhs_hi - rhs_lo.
+        reduce_signs_parallelized (:257-280) is the tree of 4 * high + low -> comparison_reduction_lut."""
+        assert lhs.num_blocks == rhs.num_blocks and lhs.num_blocks > 0
+        nb, m = lhs.num_blocks, self.msg
+        assert all(d < m for d in lhs.degree + rhs.degree)
+        sign_lut = self._lut(("sign",), lambda x: int(x != 0))
+        chunks = [[j] for j in range(nb)] if self.carry < m else [list(range(j, min(j + 2, nb))) for j in range(0, nb, 2)]
+        signs = self._new(lhs.count, len(chunks))
+        layer = _PbsLayer(self)
+        for c, chunk in enumerate(chunks):
+            if len(chunk) == 2:
+                lo, hi = chunk
+                terms = [(lhs, hi, m), (lhs, lo, 1), (rhs, hi, -m), (rhs, lo, -1)]
+            else:
+                terms = [(lhs, chunk[0], 1), (rhs, chunk[0], -1)]
+            layer.add(signs, c, sign_lut, prepare=(0, terms), post_add=1)
+        layer.flush()
+        table = [IS_INFERIOR] * 5 + [IS_EQUAL] + [IS_SUPERIOR] * 5      # comparator.rs:81-100, index 4 * high + low
+        reduction = self._lut(("sign_reduction",), lambda x: table[x] if x < len(table) else 0)
+        blocks = [(signs, c) for c in range(len(chunks))]
+        while len(blocks) != 1:
+            out = self._new(lhs.count, len(blocks) // 2)
+            for c in range(len(blocks) // 2):
+                (low, lj), (high, hj) = blocks[2 * c], blocks[2 * c + 1]
+                assert 4 * high.degree[hj] + low.degree[lj] < self.msg * self.carry
+                layer.add(out, c, reduction, prepare=(0, [(high, hj, 4), (low, lj, 1)]))
+            layer.flush()
+            blocks = [(out, c) for c in range(len(blocks) // 2)] + (blocks[-1:] if len(blocks) % 2 else [])
+        return blocks[0]
+
+    _ORDER = {"gt": lambda x: x == IS_SUPERIOR, "ge": lambda x: x in (IS_EQUAL, IS_SUPERIOR),
+              "lt": lambda x: x == IS_INFERIOR, "le": lambda x: x in (IS_EQUAL, IS_INFERIOR)}
+
+    def _unchecked_order(self, name: str, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
+        """unchecked_{gt,ge,lt,le}_parallelized (comparator.rs:1079-1125): the sign, then map_sign_result
+        (:957-971)."""
+        self._require(f"unchecked_{name}_parallelized", self.comparison_refusal)
+        lhs, rhs = self._resident(lhs), self._resident(rhs)
+        sign, sj = self._unchecked_compare(lhs, rhs)
+        res = self._new(lhs.count, 1)
+        layer = _PbsLayer(self)
+        layer.add(res, 0, self._lut(("sign_is", name), lambda x, f=self._ORDER[name]: int(f(x))),
+                  prepare=(0, [(sign, sj, 1)]))
+        layer.flush()
+        return res
+
+    def _order(self, name: str, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
+        """{gt,ge,lt,le}_parallelized (comparator.rs:1267-1393)."""
+        self._require(f"{name}_parallelized", self.comparison_refusal)
+        return self._unchecked_order(name, self._clean(lhs), self._clean(rhs))
+
+    def unchecked_gt_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._unchecked_order("gt", lhs, rhs)
+
+    def unchecked_ge_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._unchecked_order("ge", lhs, rhs)
+
+    def unchecked_lt_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._unchecked_order("lt", lhs, rhs)
+
+    def unchecked_le_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._unchecked_order("le", lhs, rhs)
+
+    def gt_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._order("gt", lhs, rhs)
+
+    def ge_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._order("ge", lhs, rhs)
+
+    def lt_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._order("lt", lhs, rhs)
+
+    def le_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._order("le", lhs, rhs)
+
+    # -- select -----------------------------------------------------------------------------------------------
+    def _zero_out_if(self, layer: _PbsLayer, ct: RadixBatch, cond: RadixBatch, cj: int, key, predicate) -> RadixBatch:
+        """zero_out_if (radix_parallel/cmux.rs:281-316) on a clone of ct, its PBS requests queued on `layer`: a
+        condition of degree 0 decides on the spot, blocks of degree 0 are skipped."""
+        assert cond.degree[cj] < self.msg
+        res = ct.clone()
+        if cond.degree[cj] == 0:
+            if predicate(0):
+                for j in range(res.num_blocks):   # create_trivial_zero_assign_radix
+                    self._set_trivial(res, j, 0)
+            return res
+        lut = self._lut(("zero_out_if", key), lambda block, c: 0 if predicate(c) else block, bivariate=True)
+        for j in range(res.num_blocks):
+            if res.degree[j] != 0:
+                assert res.degree[j] < self.msg
+                layer.add(res, j, lut, prepare=(0, [(res, j, self.msg), (cond, cj, 1)]))
+        return res
+
+    def _programmable_if_then_else(self, cond: RadixBatch, cj: int, true_ct: RadixBatch, false_ct: RadixBatch, key,
+                                   predicate) -> RadixBatch:
+        """unchecked_programmable_if_then_else_parallelized (cmux.rs:194-248), do_clean_message = true: both
+        zero_out_if in one PBS layer (the reference joins them), then add and message_extract in a second."""
+        layer = _PbsLayer(self)
+        t = self._zero_out_if(layer, true_ct, cond, cj, (key, False), lambda x: not predicate(x))
+        f = self._zero_out_if(layer, false_ct, cond, cj, (key, True), predicate)
+        layer.flush()
+        for j in range(t.num_blocks):
+            layer.add(t, j, self.lut_message, prepare=(0, [(t, j, 1), (f, j, 1)]))
+        layer.flush()
+        return t
+
+    def unchecked_if_then_else_parallelized(self, condition: RadixBatch, true_ct: RadixBatch,
+                                            false_ct: RadixBatch) -> RadixBatch:
+        """cmux.rs:7-25: condition is a BooleanBlock, a one-block batch of degree <= 1."""
+        self._require("unchecked_if_then_else_parallelized", self.bivariate_refusal)
+        condition, true_ct, false_ct = self._resident(condition), self._resident(true_ct), self._resident(false_ct)
+        assert condition.num_blocks == 1 and condition.degree[0] <= 1 and true_ct.num_blocks == false_ct.num_blocks
+        return self._programmable_if_then_else(condition, 0, true_ct, false_ct, "true", lambda x: x == 1)
+
+    def if_then_else_parallelized(self, condition: RadixBatch, true_ct: RadixBatch, false_ct: RadixBatch) -> RadixBatch:
+        """cmux.rs:72-97."""
+        self._require("if_then_else_parallelized", self.bivariate_refusal)
+        return self.unchecked_if_then_else_parallelized(condition, self._clean(true_ct), self._clean(false_ct))
+
+    cmux_parallelized = if_then_else_parallelized   # cmux.rs:102-107
+
+    # -- min / max ----------------------------------------------------------------------------------------------
+    def _unchecked_min_or_max(self, name: str, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
+        """Comparator::unchecked_min_or_max_parallelized (comparator.rs:849-875): the sign, then the programmable
+        cmux on it (max keeps lhs where the sign is IS_SUPERIOR, min where it is IS_INFERIOR)."""
+        self._require(f"unchecked_{name}_parallelized", self.comparison_refusal or self.bivariate_refusal)
+        lhs, rhs = self._resident(lhs), self._resident(rhs)
+        sign, sj = self._unchecked_compare(lhs, rhs)
+        keep = IS_SUPERIOR if name == "max" else IS_INFERIOR
+        return self._programmable_if_then_else(sign, sj, lhs, rhs, name, lambda x: x == keep)
+
+    def unchecked_max_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._unchecked_min_or_max("max", lhs, rhs)
+
+    def unchecked_min_parallelized(self, lhs, rhs) -> RadixBatch:
+        return self._unchecked_min_or_max("min", lhs, rhs)
+
+    def max_parallelized(self, lhs, rhs) -> RadixBatch:
+        """comparator.rs:1395-1426."""
+        self._require("max_parallelized", self.comparison_refusal or self.bivariate_refusal)
+        return self._unchecked_min_or_max("max", self._clean(lhs), self._clean(rhs))
+
+    def min_parallelized(self, lhs, rhs) -> RadixBatch:
+        """comparator.rs:1428-1459."""
+        self._require("min_parallelized", self.comparison_refusal or self.bivariate_refusal)
+        return self._unchecked_min_or_max("min", self._clean(lhs), self._clean(rhs))
 
 
 # ---- integer WoP-PBS (integer/wopbs/mod.rs) ----------------------------------------------------------
