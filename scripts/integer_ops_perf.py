@@ -14,7 +14,11 @@ tfhe_mi355_lwe_scalar_mul_add_async calls (a copy of the first term, a scale, th
 plaintext add on the body through torch), alternating with the fused arm in every round; both arms' outputs are
 compared first.  This unfused arm lives in this script only.
 
-usage: integer_ops_perf.py [--out result.json] [--quick]
+--family shift measures the operations of DESIGN.md 5.6c instead, by the same method and without the unfused arm:
+scalar_left_shift and scalar_rotate_right by 5, left_shift and rotate_left by an encrypted amount, scalar_mul by 5
+and by 0xDEADBEEF (profiles/integer_shift_perf_2_2.json).
+
+usage: integer_ops_perf.py [--family ops|shift] [--out result.json] [--quick]
 """
 import argparse
 import json
@@ -33,6 +37,8 @@ from tfhe_mi355.parameters import PARAM_MESSAGE_2_CARRY_2_KS_PBS as P  # noqa: E
 
 BLOCKS = 16
 OPS = ("sub", "lt", "eq", "bitand", "max", "if_then_else")
+SHIFT_OPS = ("scalar_left_shift_5", "scalar_rotate_right_5", "left_shift", "rotate_left", "scalar_mul_5",
+             "scalar_mul_0xDEADBEEF")
 ROUNDS = 7
 
 
@@ -112,6 +118,22 @@ def calls_of(sks, K, rng, cks):
     return calls, (a, b)
 
 
+def shift_calls_of(sks, K, rng, cks):
+    M = 1 << 32
+    a = sks.to_device(cks.encrypt(rng.integers(0, M, K, dtype=np.uint64)))
+    amount = sks.to_device(cks.encrypt(rng.integers(0, 32, K, dtype=np.uint64)))
+    calls = {
+        "scalar_left_shift_5": lambda: sks.scalar_left_shift_parallelized(a, 5),
+        "scalar_rotate_right_5": lambda: sks.scalar_rotate_right_parallelized(a, 5),
+        "left_shift": lambda: sks.left_shift_parallelized(a, amount),
+        "rotate_left": lambda: sks.rotate_left_parallelized(a, amount),
+        "scalar_mul_5": lambda: sks.scalar_mul_parallelized(a, 5),
+        "scalar_mul_0xDEADBEEF": lambda: sks.scalar_mul_parallelized(a, 0xDEADBEEF),
+    }
+    assert tuple(calls) == SHIFT_OPS
+    return calls, (a, amount)
+
+
 def isolated_rate(sks, rows, reps):
     """KS+PBS/s of one engine call on `rows` rows (one LUT), the same entry point the layers use"""
     eng, ops = sks.ops.eng, sks.ops
@@ -124,8 +146,8 @@ def isolated_rate(sks, rows, reps):
     return rows / statistics.median(timed(f, reps) for _ in range(ROUNDS))
 
 
-def measure(sks, cks, K, reps, rng):
-    calls, (a, b) = calls_of(sks, K, rng, cks)
+def measure(sks, cks, K, reps, rng, family="ops"):
+    calls, (a, b) = (calls_of if family == "ops" else shift_calls_of)(sks, K, rng, cks)
     res = {"K": K, "reps_per_window": reps, "rounds": ROUNDS, "ops": {}}
     counts = {}
     for name, f in calls.items():   # warm-up: LUTs, layer tables, scratch; and the counters
@@ -134,10 +156,11 @@ def measure(sks, cks, K, reps, rng):
         counts[name] = (sks.pbs_count, sks.launches)
     fused = sks.ops.block_layer
     unfused = unfused_block_layer(sks.ops)
-    want = sks.to_host(calls["lt"]())
-    sks.ops.block_layer = unfused
-    same = bool(np.array_equal(sks.to_host(calls["lt"]()).data, want.data))
-    sks.ops.block_layer = fused
+    if "lt" in calls:
+        want = sks.to_host(calls["lt"]())
+        sks.ops.block_layer = unfused
+        same = bool(np.array_equal(sks.to_host(calls["lt"]()).data, want.data))
+        sks.ops.block_layer = fused
     samples = {name: [] for name in list(calls) + ["lt_unfused"]}
     for _ in range(ROUNDS):
         for name, f in calls.items():
@@ -159,6 +182,8 @@ def measure(sks, cks, K, reps, rng):
             "effective_pbs_per_s": pbs / med, "mean_rows_per_layer": rows, "isolated_ks_pbs_per_s": rates[rows],
             "fraction_of_isolated": pbs / med / rates[rows],
         }
+    if "lt" not in calls:
+        return res
     u = statistics.median(samples["lt_unfused"])
     f_ = statistics.median(samples["lt"])
     res["lt_unfused"] = {"outputs_equal_fused": same, "ms_per_call": 1e3 * u, "min_ms": 1e3 * min(samples["lt_unfused"]),
@@ -169,10 +194,13 @@ def measure(sks, cks, K, reps, rng):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "integer_ops_perf_2_2.json"))
+    ap.add_argument("--family", choices=("ops", "shift"), default="ops")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="one short window per arm: a rehearsal, not a measurement")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU: there is no CPU fall-back"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", f"integer_{args.family}_perf_2_2.json")
     if args.quick:
         ROUNDS = 1
     def say(text):
@@ -189,12 +217,20 @@ if __name__ == "__main__":
     x, y = sks.to_device(cks.encrypt(v[0])), sks.to_device(cks.encrypt(v[1]))
     assert [int(t) for t in integer.ClientKey(ck, 1).decrypt(sks.to_host(sks.lt_parallelized(x, y)))] == [1, 0]
     assert [int(t) for t in cks.decrypt(sks.to_host(sks.sub_parallelized(x, y)))] == [(5 - 7) % (1 << 32), (1 << 31) - 3]
+    if args.family == "shift":   # and of the new family: a shift by an encrypted amount and a scalar_mul decrypt
+        amount = sks.to_device(cks.encrypt(np.array([3, 31], dtype=np.uint64)))
+        assert [int(t) for t in cks.decrypt(sks.to_host(sks.left_shift_parallelized(x, amount)))] == [5 << 3, 0]
+        assert [int(t) for t in cks.decrypt(sks.to_host(sks.scalar_rotate_right_parallelized(x, 5)))] == \
+            [(5 >> 5) | ((5 << 27) & 0xFFFFFFFF), 1 << 26]
+        assert [int(t) for t in cks.decrypt(sks.to_host(sks.scalar_mul_parallelized(x, 0xDEADBEEF)))] == \
+            [(5 * 0xDEADBEEF) % (1 << 32), ((1 << 31) * 0xDEADBEEF) % (1 << 32)]
     say("lt and sub decrypt; measuring")
     runs = []
     for K, reps in ((256, 3), (1, 20)):
-        runs.append(measure(sks, cks, K, 1 if args.quick else reps, rng))
+        runs.append(measure(sks, cks, K, 1 if args.quick else reps, rng, args.family))
         say(f"K = {K} done")
-    result = {"device": torch.cuda.get_device_name(0), "parameters": P.name, "blocks": BLOCKS, "runs": runs}
+    result = {"family": args.family, "device": torch.cuda.get_device_name(0), "parameters": P.name, "blocks": BLOCKS,
+              "runs": runs}
     text = json.dumps(result, indent=1)
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -18,6 +18,10 @@ operand pairs at once:
   ServerKey neg, sub, bitand / bitor / bitxor / bitnot, eq / ne, gt / ge / lt / le, if_then_else / cmux, min / max
   (unchecked and default forms, unsigned)                   radix/neg.rs, radix_parallel/{neg,sub,bitwise_op,comparison,
                                                             cmux}.rs, comparator.rs: see "neg, sub, ..." in ServerKey
+  ServerKey scalar_{left_shift,right_shift,rotate_left,rotate_right}, {left_shift,right_shift,rotate_left,
+  rotate_right} by an encrypted amount (barrel_shifter), scalar_mul (unchecked and default forms, unsigned)
+                                                            radix_parallel/{scalar_shift,scalar_rotate,shift,rotate,
+                                                            bit_extractor,scalar_mul}.rs
   shortint unchecked_apply_lookup_table_bivariate_assign    shortint/server_key/bivariate_pbs.rs:69-182
   WopbsKey (wopbs, wopbs_without_padding, bivariate_wopbs_with_degree, generate_lut_radix,
   generate_lut_radix_without_padding, generate_lut_bivariate_radix, keyswitch_to_wopbs_params,
@@ -477,6 +481,13 @@ def comparison_refusal(msg: int, carry: int):
     return None
 
 
+def barrel_shifter_refusal(msg: int, carry: int):
+    """barrel_shifter's assert (radix_parallel/shift.rs:334-337): the mux input control | b | a takes 3 bits."""
+    if (msg.bit_length() - 1) + (carry.bit_length() - 1) < 3:
+        return "fewer than 3 bits (message + carry) in a block: the barrel shifter's mux input does not fit"
+    return None
+
+
 IS_INFERIOR, IS_EQUAL, IS_SUPERIOR = 0, 1, 2   # comparator.rs:43-45
 _NEG1 = (1 << 64) - 1
 
@@ -526,6 +537,8 @@ class ServerKey:
         self.mul_refusal = self.propagation_refusal or mul_refusal(m, self.carry)
         self.bivariate_refusal = bivariate_refusal(m, self.carry)
         self.comparison_refusal = comparison_refusal(m, self.carry)
+        self.barrel_shifter_refusal = barrel_shifter_refusal(m, self.carry)
+        self.bits = m.bit_length() - 1          # message bits per block
         self._luts = {}   # the LUTs of neg .. min / max, built on first use: (name, ...) -> LookupTable
 
     def _require(self, op: str, refusal):
@@ -789,8 +802,8 @@ class ServerKey:
     # layer is a fused _PbsLayer (flush_fused): the block arithmetic the reference does between two layers --
     # pack_block_chunk, the LWE subtraction of compare_block_assign, 4 * high + low of the sign tree, the sums
     # of eq / ne, the bivariate packing -- is the prepare op of the request that consumes it.  A BooleanBlock
-    # is a one-block RadixBatch of degree <= 1.  Out of scope: signed integers, scalar operands, overflowing
-    # sub, shifts / rotations / div / abs and the smart_* forms.
+    # is a one-block RadixBatch of degree <= 1.  Out of scope: signed integers, scalar add / sub / bitwise ops /
+    # comparisons, overflowing sub, div / abs and the smart_* forms.
     def _lut(self, key, f, bivariate: bool = False) -> LookupTable:
         """One LookupTable object per function for the life of the key: the device caches go by identity."""
         t = self._luts.get(key)
@@ -1128,6 +1141,274 @@ class ServerKey:
         """comparator.rs:1428-1459."""
         self._require("min_parallelized", self.comparison_refusal or self.bivariate_refusal)
         return self._unchecked_min_or_max("min", self._clean(lhs), self._clean(rhs))
+
+    # ---- shifts and rotations by a clear amount, by an encrypted amount, scalar_mul -------------------------------
+    # Every PBS layer is a fused _PbsLayer again.  A block rotation is never a data movement: it is the source block
+    # index of the prepare terms, and the outputs are scattered into a fresh batch, so no op of a block-layer call
+    # reads a block another op of the same call writes.  A clear operand is one non-negative Python int for the
+    # whole batch: the DAG depends on its value.
+    _SHIFTS = ("left_shift", "right_shift", "rotate_left", "rotate_right")
+
+    @staticmethod
+    def _clear_operand(op: str, value) -> int:
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise TypeError(f"integer {op}: the clear operand is one Python int for the whole batch, "
+                            f"got {type(value).__name__}")
+        if value < 0:
+            raise ValueError(f"integer {op}: the clear operand must not be negative, got {value}")
+        return int(value)
+
+    @staticmethod
+    def _assign(ct: RadixBatch, res: RadixBatch):
+        if res is not ct:
+            ct.data, ct.degree, ct.noise = res.data, list(res.degree), list(res.noise)
+
+    def _scalar_shift_luts(self, op: str, within: int):
+        """(LUT of a window, LUT of a shift's end block) for a shift of `within` bits inside the blocks.
+        left_shift (scalar_shift.rs:603-615) packs previous * msg + current, the other three pack the block that
+        stays * msg + the neighbour that gives bits: right_shift (:342-357) current * msg + next, the rotations
+        (scalar_rotate.rs:309-324, 644-654) receiver * msg + giver.  The end block of a shift takes shortint
+        scalar_left_shift_assign / scalar_right_shift_assign (shortint/server_key/shift.rs:411-415, 145-148)."""
+        m, bits, w = self.msg, self.bits, within
+        if op == "left_shift":
+            window = lambda previous, current: ((current << w) % m) + ((previous << w) // m)
+            end = self._lut((op, w, "end"), lambda x: (x << w) % m)
+        elif op == "rotate_left":
+            window, end = (lambda receiver, giver: ((receiver << w) % m) + ((giver << w) // m)), None
+        else:
+            window = lambda current, giver: (current >> w) + (((giver << bits) >> w) % m)
+            end = self._lut((op, w, "end"), lambda x: ((x % m) >> w) % m) if op == "right_shift" else None
+        return self._lut((op, w), window, bivariate=True), end
+
+    def _scalar_shift_queue(self, layer: _PbsLayer, ct: RadixBatch, op: str, amount: int) -> RadixBatch:
+        """unchecked_scalar_{left,right}_shift_assign_parallelized (scalar_shift.rs:553-647, 246-368) and
+        unchecked_scalar_rotate_{left,right}_assign_parallelized (scalar_rotate.rs:611-681, 272-350) into a fresh
+        batch; the PBS requests are queued on `layer` (the caller flushes it: scalar_mul shares one layer among its
+        preshifts).  amount mod T == 0 returns ct itself.  Result block j reads block j -+ rotations of ct: the
+        blocks a shift vacates are trivial zeros.  With nothing to shift inside the blocks there is no PBS: one
+        block-layer call copies the blocks to their places."""
+        nb, bits, m = ct.num_blocks, self.bits, self.msg
+        assert nb > 0 and ct.block_carries_are_empty(m)
+        amount %= bits * nb
+        if amount == 0:
+            return ct
+        rot, within = divmod(amount, bits)
+        left, shift = op in ("left_shift", "rotate_left"), op in ("left_shift", "right_shift")
+        step = -rot if left else rot                  # rotate_right(rot) of the blocks for the left forms
+
+        def source(j):
+            """the block of ct that stands at place j after the block rotation; None: a vacated place"""
+            i = j + step
+            return i % nb if not shift or 0 <= i < nb else None
+
+        if within == 0:
+            res = self._new(ct.count, nb)
+            moves = []
+            for j in range(nb):
+                i = source(j)
+                moves.append((self.ops.block(res, j), 0, [] if i is None else [(self.ops.block(ct, i), 1)]))
+                if i is not None:
+                    res.degree[j], res.noise[j] = ct.degree[i], ct.noise[i]
+            self.ops.block_layer(moves)
+            return res
+        window, end = self._scalar_shift_luts(op, within)
+        res = self.create_trivial_zero(ct.count, nb) if shift and rot else self._new(ct.count, nb)
+        giver = -1 if left else 1                     # the neighbour a place takes bits from
+        for j in range(nb):
+            i = source(j)
+            g = source(j + giver) if not shift or 0 <= j + giver < nb else None
+            if i is None:
+                continue
+            if g is None:                             # the end block of a shift pulls in zeros
+                layer.add(res, j, end, prepare=(0, [(ct, i, 1)]))
+            elif op == "left_shift":
+                layer.add(res, j, window, prepare=(0, [(ct, g, m), (ct, i, 1)]))
+            else:
+                layer.add(res, j, window, prepare=(0, [(ct, i, m), (ct, g, 1)]))
+        return res
+
+    def _unchecked_scalar_shift(self, op: str, ct: RadixBatch, amount, assign: bool = False) -> RadixBatch:
+        name = f"unchecked_scalar_{op}{'_assign' if assign else ''}_parallelized"
+        amount = self._clear_operand(name, amount)
+        self._require(name, self.bivariate_refusal)
+        layer = _PbsLayer(self)
+        res = self._scalar_shift_queue(layer, self._resident(ct), op, amount)
+        layer.flush()
+        return res
+
+    def _scalar_shift(self, op: str, ct: RadixBatch, amount, assign: bool) -> RadixBatch:
+        """scalar_{left_shift,right_shift,rotate_left,rotate_right}[_assign]_parallelized (scalar_shift.rs:451-461,
+        732-742, scalar_rotate.rs): full_propagate first when the operand has carries, on the operand itself in
+        the assign form and on a clone otherwise."""
+        name = f"scalar_{op}{'_assign' if assign else ''}_parallelized"
+        amount = self._clear_operand(name, amount)
+        self._require(name, self.bivariate_refusal)
+        if not assign:
+            return self._unchecked_scalar_shift(op, self._clean(ct), amount)
+        if not ct.block_carries_are_empty(self.msg):
+            self.full_propagate(ct)
+        self._assign(ct, self._unchecked_scalar_shift(op, ct, amount))
+        return ct
+
+    # -- encrypted amount -------------------------------------------------------------------------------------------
+    def _barrel_shifter(self, ct: RadixBatch, shift: RadixBatch, operation: str) -> RadixBatch:
+        """barrel_shifter (radix_parallel/shift.rs:321-473) into a fresh batch.  Layer 1 extracts every bit of ct
+        (BitExtractor, bit_extractor.rs:52-67) and the first s bits of shift, born at bit 2
+        (with_final_offset(.., 2)); the reference joins the two extractions.  One layer per control bit d follows:
+        bit i becomes mux_lut(2 * b + a + control_d), a = bit i, b = bit i -+ 2^d (mod T, or the padding -- a
+        trivial zero, so no term -- where a shift pulls it in); a stage reads the bits of the stage before and
+        writes a fresh batch.  The last layer recomposes sum_i 2^i * bit_i per block under lut_message."""
+        nb, bits = ct.num_blocks, self.bits
+        assert ct.block_carries_are_empty(self.msg) and shift.block_carries_are_empty(self.msg)
+        T = bits * nb
+        s = T.bit_length() - 1 + (1 if T & (T - 1) else 0)          # shift.rs:345-353
+        K = ct.count
+        a, control = self._new(K, T), self._new(K, s)
+        layer = _PbsLayer(self)
+        for n in range(T):
+            layer.add(a, n, self._lut(("bit", n % bits, 0), lambda x, i=n % bits: (x >> i) & 1),
+                      prepare=(0, [(ct, n // bits, 1)]))
+        for n in range(s):
+            layer.add(control, n, self._lut(("bit", n % bits, 2), lambda x, i=n % bits: ((x >> i) & 1) << 2),
+                      prepare=(0, [(shift, n // bits, 1)]))
+        layer.flush()
+        mux = self._lut(("mux",), lambda x: (x >> 1) & 1 if (x >> 2) & 1 else x & 1)
+        left, rotate = operation in ("left_shift", "rotate_left"), operation in ("rotate_left", "rotate_right")
+        for d in range(s):
+            out = self._new(K, T)
+            for i in range(T):
+                b = i - (1 << d) if left else i + (1 << d)
+                terms = [(a, b % T, 2)] if rotate or 0 <= b < T else []
+                assert 2 * 1 + a.degree[i] + control.degree[d] < self.msg * self.carry      # control | b | a
+                layer.add(out, i, mux, prepare=(0, terms + [(a, i, 1), (control, d, 1)]))
+            layer.flush()
+            a = out
+        res = self._new(K, nb)
+        for j in range(nb):
+            layer.add(res, j, self.lut_message, prepare=(0, [(a, j * bits + i, 1 << i) for i in range(bits)]))
+        layer.flush()
+        return res
+
+    def _encrypted_shift(self, op: str, ct: RadixBatch, shift: RadixBatch, unchecked: bool, assign: bool) -> RadixBatch:
+        """{unchecked_,}{left_shift,right_shift,rotate_left,rotate_right}[_assign]_parallelized (shift.rs:20-298,
+        rotate.rs).  The default forms propagate whichever operand has carries: shift on a clone, ct itself in the
+        assign form and on a clone otherwise.  The reference takes the block count of shift for both operands and
+        panics on its closing assert when they differ (shift.rs:329, 457): a ValueError here."""
+        name = f"{'unchecked_' if unchecked else ''}{op}{'_assign' if assign else ''}_parallelized"
+        self._require(name, self.barrel_shifter_refusal)
+        if ct.num_blocks != shift.num_blocks or ct.num_blocks == 0:
+            raise ValueError(f"integer {name}: the value has {ct.num_blocks} blocks and the amount {shift.num_blocks}; "
+                             "the barrel shifter takes operands of the same, non-zero block count")
+        if ct.count != shift.count:
+            raise ValueError(f"integer {name}: {ct.count} values against {shift.count} amounts")
+        if unchecked:
+            ct_in, shift = self._resident(ct), self._resident(shift)
+        else:
+            shift = self._clean(shift)
+            if assign and not ct.block_carries_are_empty(self.msg):
+                self.full_propagate(ct)
+            ct_in = self._clean(ct)
+        res = self._barrel_shifter(ct_in, shift, op)
+        if assign:
+            self._assign(ct, res)
+            return ct
+        return res
+
+    # -- scalar_mul ---------------------------------------------------------------------------------------------------
+    def _require_scalar_mul(self, name: str, scalar: int):
+        """0 and 1 need nothing, a power of two the shift's bivariate layer, the rest the chunked sum as well"""
+        if scalar > 1:
+            self._require(name, self.bivariate_refusal or (self.propagation_refusal if scalar & (scalar - 1) else None))
+
+    def _unchecked_scalar_mul(self, name: str, ct: RadixBatch, scalar: int) -> RadixBatch:
+        """unchecked_scalar_mul_assign_parallelized (radix_parallel/scalar_mul.rs:330-397) into a fresh batch (ct
+        itself for scalar 1).  One deviation: a power of two 2^e with e >= T gives trivial zeros, the product
+        modulo 2^T, where the reference shifts by e mod T (:346-350 over scalar_shift.rs:576)."""
+        self._require_scalar_mul(name, scalar)
+        ct = self._resident(ct)
+        nb, bits = ct.num_blocks, self.bits
+        if scalar == 0 or nb == 0:
+            return self.create_trivial_zero(ct.count, nb)
+        if scalar == 1:
+            return ct
+        if scalar & (scalar - 1) == 0:
+            e = scalar.bit_length() - 1
+            if e >= bits * nb:
+                return self.create_trivial_zero(ct.count, nb)
+            return self._unchecked_scalar_shift("left_shift", ct, e)
+        scalar_bits = [(scalar >> i) & 1 for i in range(scalar.bit_length())]   # LSB first, up to the last set bit
+        needed = {i % bits for i, bit in enumerate(scalar_bits) if bit}          # has_at_least_one_set
+        layer = _PbsLayer(self)
+        preshifted = {w: self._scalar_shift_queue(layer, ct, "left_shift", w) for w in sorted(needed)}
+        layer.flush()                                    # the reference's par_iter over the shifts: one layer
+        terms = [self.blockshift(preshifted[i % bits], i // bits)
+                 for i, bit in enumerate(scalar_bits[:bits * nb]) if bit]
+        out = self.unchecked_sum_ciphertexts_vec(terms)
+        return out if out is not None else self.create_trivial_zero(ct.count, nb)
+
+    def unchecked_scalar_mul_parallelized(self, ct: RadixBatch, scalar) -> RadixBatch:
+        name = "unchecked_scalar_mul_parallelized"
+        return self._unchecked_scalar_mul(name, ct, self._clear_operand(name, scalar))
+
+    def unchecked_scalar_mul_assign_parallelized(self, ct: RadixBatch, scalar):
+        name = "unchecked_scalar_mul_assign_parallelized"
+        self._assign(ct, self._unchecked_scalar_mul(name, ct, self._clear_operand(name, scalar)))
+
+    def scalar_mul_parallelized(self, ct: RadixBatch, scalar) -> RadixBatch:
+        """scalar_mul.rs:483-491."""
+        name = "scalar_mul_parallelized"
+        scalar = self._clear_operand(name, scalar)
+        self._require_scalar_mul(name, scalar)
+        return self._unchecked_scalar_mul(name, self._clean(ct), scalar)
+
+    def scalar_mul_assign_parallelized(self, ct: RadixBatch, scalar):
+        """scalar_mul.rs:493-503."""
+        name = "scalar_mul_assign_parallelized"
+        scalar = self._clear_operand(name, scalar)
+        self._require_scalar_mul(name, scalar)
+        if not ct.block_carries_are_empty(self.msg):
+            self.full_propagate(ct)
+        self._assign(ct, self._unchecked_scalar_mul(name, ct, scalar))
+
+
+def _add_shift_methods():
+    """the public names of the sixteen scalar and the sixteen encrypted forms"""
+    def scalar(op, unchecked, assign):
+        if unchecked and assign:
+            def f(self, ct, amount):
+                self._assign(ct, self._unchecked_scalar_shift(op, ct, amount, True))
+        elif unchecked:
+            def f(self, ct, amount):
+                return self._unchecked_scalar_shift(op, ct, amount)
+        elif assign:
+            def f(self, ct, amount):
+                self._scalar_shift(op, ct, amount, True)
+        else:
+            def f(self, ct, amount):
+                return self._scalar_shift(op, ct, amount, False)
+        return f
+
+    def encrypted(op, unchecked, assign):
+        if assign:
+            def f(self, ct, shift):
+                self._encrypted_shift(op, ct, shift, unchecked, True)
+        else:
+            def f(self, ct, shift):
+                return self._encrypted_shift(op, ct, shift, unchecked, False)
+        return f
+
+    for op in ServerKey._SHIFTS:
+        for unchecked in (True, False):
+            for assign in (True, False):
+                tail = f"{op}{'_assign' if assign else ''}_parallelized"
+                forms = ((f"scalar_{tail}", scalar(op, unchecked, assign)), (tail, encrypted(op, unchecked, assign)))
+                for name, f in forms:
+                    name = ("unchecked_" if unchecked else "") + name
+                    f.__name__ = f.__qualname__ = name
+                    setattr(ServerKey, name, f)
+
+
+_add_shift_methods()
 
 
 # ---- integer WoP-PBS (integer/wopbs/mod.rs) ----------------------------------------------------------
