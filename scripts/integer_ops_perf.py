@@ -18,7 +18,12 @@ compared first.  This unfused arm lives in this script only.
 scalar_left_shift and scalar_rotate_right by 5, left_shift and rotate_left by an encrypted amount, scalar_mul by 5
 and by 0xDEADBEEF (profiles/integer_shift_perf_2_2.json).
 
-usage: integer_ops_perf.py [--family ops|shift] [--out result.json] [--quick]
+--family div measures the operations of DESIGN.md 5.6d, again by the same method: div_rem and
+unsigned_overflowing_sub (profiles/integer_div_perf_2_2.json).  A division is a couple of hundred dependent layers, so
+its windows are a sixth as many calls; at K = 1 its time per call is put next to launches x the single-layer time of
+a one-launch operation measured in the same process (scalar_left_shift by 5, the 2.6 ms of the shift family).
+
+usage: integer_ops_perf.py [--family ops|shift|div] [--out result.json] [--quick]
 """
 import argparse
 import json
@@ -39,6 +44,7 @@ BLOCKS = 16
 OPS = ("sub", "lt", "eq", "bitand", "max", "if_then_else")
 SHIFT_OPS = ("scalar_left_shift_5", "scalar_rotate_right_5", "left_shift", "rotate_left", "scalar_mul_5",
              "scalar_mul_0xDEADBEEF")
+DIV_OPS = ("div_rem", "unsigned_overflowing_sub")
 ROUNDS = 7
 
 
@@ -134,6 +140,18 @@ def shift_calls_of(sks, K, rng, cks):
     return calls, (a, amount)
 
 
+def div_calls_of(sks, K, rng, cks):
+    M = 1 << 32
+    a = sks.to_device(cks.encrypt(rng.integers(0, M, K, dtype=np.uint64)))
+    b = sks.to_device(cks.encrypt(rng.integers(1, 1 << 16, K, dtype=np.uint64)))
+    calls = {
+        "div_rem": lambda: sks.div_rem_parallelized(a, b),
+        "unsigned_overflowing_sub": lambda: sks.unsigned_overflowing_sub_parallelized(a, b),
+    }
+    assert tuple(calls) == DIV_OPS
+    return calls, (a, b)
+
+
 def isolated_rate(sks, rows, reps):
     """KS+PBS/s of one engine call on `rows` rows (one LUT), the same entry point the layers use"""
     eng, ops = sks.ops.eng, sks.ops
@@ -147,7 +165,8 @@ def isolated_rate(sks, rows, reps):
 
 
 def measure(sks, cks, K, reps, rng, family="ops"):
-    calls, (a, b) = (calls_of if family == "ops" else shift_calls_of)(sks, K, rng, cks)
+    calls, (a, b) = {"ops": calls_of, "shift": shift_calls_of, "div": div_calls_of}[family](sks, K, rng, cks)
+    window = {name: max(1, reps // 6) if name == "div_rem" else reps for name in calls}
     res = {"K": K, "reps_per_window": reps, "rounds": ROUNDS, "ops": {}}
     counts = {}
     for name, f in calls.items():   # warm-up: LUTs, layer tables, scratch; and the counters
@@ -164,7 +183,7 @@ def measure(sks, cks, K, reps, rng, family="ops"):
     samples = {name: [] for name in list(calls) + ["lt_unfused"]}
     for _ in range(ROUNDS):
         for name, f in calls.items():
-            samples[name].append(timed(f, reps))
+            samples[name].append(timed(f, window[name]))
             if name == "lt":
                 sks.ops.block_layer = unfused
                 samples["lt_unfused"].append(timed(f, reps))
@@ -180,8 +199,17 @@ def measure(sks, cks, K, reps, rng, family="ops"):
             "ms_per_call": 1e3 * med, "min_ms": 1e3 * min(samples[name]), "max_ms": 1e3 * max(samples[name]),
             "operations_per_s": K / med, "pbs_per_operation": pbs / K, "launches": launches,
             "effective_pbs_per_s": pbs / med, "mean_rows_per_layer": rows, "isolated_ks_pbs_per_s": rates[rows],
-            "fraction_of_isolated": pbs / med / rates[rows],
+            "fraction_of_isolated": pbs / med / rates[rows], "calls_per_window": window[name],
         }
+    if family == "div" and K == 1:
+        shift = lambda: sks.scalar_left_shift_parallelized(a, 5)   # noqa: E731  (one fused layer of 14 rows)
+        shift()
+        layer = statistics.median(timed(shift, reps) for _ in range(ROUNDS))
+        res["single_layer_ms"] = 1e3 * layer
+        for name in calls:
+            op = res["ops"][name]
+            op["launches_x_single_layer_ms"] = op["launches"] * 1e3 * layer
+            op["ratio_to_launches_x_single_layer"] = op["ms_per_call"] / op["launches_x_single_layer_ms"]
     if "lt" not in calls:
         return res
     u = statistics.median(samples["lt_unfused"])
@@ -194,7 +222,7 @@ def measure(sks, cks, K, reps, rng, family="ops"):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--family", choices=("ops", "shift"), default="ops")
+    ap.add_argument("--family", choices=("ops", "shift", "div"), default="ops")
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="one short window per arm: a rehearsal, not a measurement")
     args = ap.parse_args()
@@ -224,6 +252,13 @@ if __name__ == "__main__":
             [(5 >> 5) | ((5 << 27) & 0xFFFFFFFF), 1 << 26]
         assert [int(t) for t in cks.decrypt(sks.to_host(sks.scalar_mul_parallelized(x, 0xDEADBEEF)))] == \
             [(5 * 0xDEADBEEF) % (1 << 32), ((1 << 31) * 0xDEADBEEF) % (1 << 32)]
+    if args.family == "div":
+        q, r = sks.div_rem_parallelized(x, y)
+        assert [int(t) for t in cks.decrypt(sks.to_host(q))] == [5 // 7, (1 << 31) // 3]
+        assert [int(t) for t in cks.decrypt(sks.to_host(r))] == [5 % 7, (1 << 31) % 3]
+        d, o = sks.unsigned_overflowing_sub_parallelized(x, y)
+        assert [int(t) for t in cks.decrypt(sks.to_host(d))] == [(5 - 7) % (1 << 32), (1 << 31) - 3]
+        assert [int(t) for t in integer.ClientKey(ck, 1).decrypt(sks.to_host(o))] == [1, 0]
     say("lt and sub decrypt; measuring")
     runs = []
     for K, reps in ((256, 3), (1, 20)):

@@ -22,6 +22,12 @@ operand pairs at once:
   rotate_right} by an encrypted amount (barrel_shifter), scalar_mul (unchecked and default forms, unsigned)
                                                             radix_parallel/{scalar_shift,scalar_rotate,shift,rotate,
                                                             bit_extractor,scalar_mul}.rs
+  ServerKey unsigned_overflowing_sub, div_rem, div, rem (unchecked and default forms, unsigned), the zero tests
+  compare_blocks_with_zero, is_at_least_one_comparisons_block_true, are_all_comparisons_block_true
+                                                            radix_parallel/{sub,div_mod,scalar_comparison}.rs,
+                                                            shortint/server_key/{sub,neg}.rs: see "overflowing
+                                                            sub, zero tests, division" in ServerKey
+  shortint generate_lookup_table_bivariate_with_factor      shortint/server_key/bivariate_pbs.rs:71-96
   shortint unchecked_apply_lookup_table_bivariate_assign    shortint/server_key/bivariate_pbs.rs:69-182
   WopbsKey (wopbs, wopbs_without_padding, bivariate_wopbs_with_degree, generate_lut_radix,
   generate_lut_radix_without_padding, generate_lut_bivariate_radix, keyswitch_to_wopbs_params,
@@ -253,6 +259,12 @@ class _HostOps:
         idx = np.repeat(np.asarray(lut_of_request, dtype=np.uint32), K)
         return self.sk.shortint.engine_ks_pbs(x, np.stack([lut.acc for lut in luts]), idx if len(luts) > 1 else None)
 
+    def plan(self, key, luts):
+        """nothing to keep on the host: every layer hands its LUTs to the engine"""
+        from contextlib import nullcontext
+
+        return nullcontext()
+
     def pbs_rows(self, todo, luts):
         K = todo[0][0].count
         x = np.concatenate([rb.data[:, j, :] for rb, j, _ in todo], axis=0)
@@ -299,11 +311,37 @@ class _BoundedCache:
         return len(self._d) + len(self._pinned)
 
 
+class _LayerPlan:
+    """The device tables of one deep DAG (a division, an overflowing sub) on one operand shape: ONE stack of
+    every LUT the DAG can ask for, the same for all its layers, and per distinct layer the int32 array of each
+    row's index into that stack.  A layer is told apart by (K, the stack positions of its requests), so the second
+    call on operands of the same shape finds every array and uploads nothing, however many layers the DAG has;
+    _DeviceOps._tables, one stack per layer in an LRU, cannot promise that beyond its capacity."""
+
+    def __init__(self, ops: "_DeviceOps", luts):
+        self.luts = list(luts)
+        self.position = {id(lut): i for i, lut in enumerate(self.luts)}
+        self.stack = ops.from_host(np.stack([lut.acc for lut in self.luts]))
+        self.indexes = {}
+
+    def serves(self, luts) -> bool:
+        return len(luts) == len(self.luts) and all(a is b for a, b in zip(luts, self.luts))
+
+    def tables(self, ops: "_DeviceOps", K, lut_of_request, luts):
+        where = tuple(self.position[id(luts[li])] for li in lut_of_request)
+        idx = self.indexes.get((K, where))
+        if idx is None:
+            idx = ops.index_from_host(np.repeat(np.asarray(where, dtype=np.int32), K))
+            self.indexes[(K, where)] = idx
+        return self.stack, len(self.luts), idx
+
+
 class _DeviceOps:
     """torch int64 tensors resident on the engine's GPU between layers; the LWE arithmetic runs in
     the engine's own kernels (lwe_ops.hip), torch only allocates, slices and copies."""
 
     CACHE_ENTRIES = 256  # distinct layer tables kept on the device (a FheUint32 multiply uses 11)
+    PLAN_ENTRIES = 8     # table plans kept on the device: one per (deep DAG, blocks, K, operand shape)
 
     def __init__(self, sk: "ServerKey"):
         import torch
@@ -316,6 +354,9 @@ class _DeviceOps:
         self._lut_dev = _BoundedCache(self.CACHE_ENTRIES, capturing)
         # LUT stacks and per-row LUT index arrays of the layers seen so far (bounded LRU)
         self._stacks = _BoundedCache(self.CACHE_ENTRIES, capturing)
+        # the table plans of the deep DAGs (division, overflowing sub), one per operand shape (bounded LRU)
+        self._plans = _BoundedCache(self.PLAN_ENTRIES, capturing)
+        self._plan = None
         self._scratch = None
 
     def zeros(self, k, b, s):
@@ -329,6 +370,29 @@ class _DeviceOps:
 
     def from_host(self, data):
         return self.torch.from_numpy(np.ascontiguousarray(data).view(np.int64)).to(self.device)
+
+    def index_from_host(self, idx):
+        """an int32 LUT-index array of a table plan: the other host-to-device copy a deep DAG makes"""
+        return self.torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(self.device)
+
+    def plan(self, key, luts):
+        """Context of one deep DAG: while it is open every batched KS+PBS takes its tables from the _LayerPlan
+        of `key` (made and uploaded the first time the key is seen) and not from _tables.  luts: every LUT the
+        DAG can ask for, in a fixed order."""
+        from contextlib import contextmanager
+
+        @contextmanager
+        def scope():
+            plan = self._plans.get(key)
+            if plan is None or not plan.serves(luts):
+                plan = _LayerPlan(self, luts)
+                self._plans.put(key, plan)
+            outer, self._plan = self._plan, plan
+            try:
+                yield plan
+            finally:
+                self._plan = outer
+        return scope()
 
     def copy_block(self, dst, j, src, i):
         dst.data[:, j, :].copy_(src.data[:, i, :])
@@ -411,12 +475,15 @@ class _DeviceOps:
         """batched KS+PBS of the rows of x (request q: rows [qK, (q+1)K), LUT lut_of_request[q]) -> new rows"""
         torch = self.torch
         n = x.shape[0]
-        d_luts, idx = self._tables(K, lut_of_request, luts)
+        if self._plan is not None:
+            d_luts, nluts, idx = self._plan.tables(self, K, lut_of_request, luts)
+        else:
+            (d_luts, idx), nluts = self._tables(K, lut_of_request, luts), len(luts)
         out = torch.empty_like(x)
         need = self.eng.ks_pbs_scratch_bytes(n)
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self.eng.keyswitch_programmable_bootstrap_async(x, out, d_luts, len(luts), n, self._scratch,
+        self.eng.keyswitch_programmable_bootstrap_async(x, out, d_luts, nluts, n, self._scratch,
                                                         d_lut_indexes=idx)
         return out
 
@@ -488,6 +555,54 @@ def barrel_shifter_refusal(msg: int, carry: int):
     return None
 
 
+BORROW_NONE, BORROW_GENERATED, BORROW_PROPAGATED = 0, 1, 2   # radix_parallel/sub.rs:11-19
+
+
+def overflowing_sub_refusal(msg: int, carry: int):
+    """Why unsigned_overflowing_sub cannot serve a modulus pair (None: it can).  Only the Hillis-Steele branch of
+    unsigned_overflowing_propagate_subtraction_borrow (sub.rs:397-421) is implemented; the conditions are the ones
+    its arithmetic needs, each stated where it is used in _overflowing_sub_steps."""
+    total = msg * carry
+    if total < 16:
+        return ("message_modulus * carry_modulus < 16: the reference propagates borrows sequentially here "
+                "(add.rs:448-462), and only the Hillis-Steele branch is implemented")
+    if 2 * msg - 1 >= total:
+        # lhs - rhs + message_modulus: a block of the difference takes one carry bit
+        return "carry_modulus < 2: a block of the difference, in 0 .. 2 * message_modulus - 1, overflows the block"
+    if BORROW_PROPAGATED + 1 > msg:
+        # the prefix sum's right operand is a borrow state (0, 1 or 2) in the message bits
+        return "a borrow state (0, 1, 2) does not fit in the message bits of the prefix-sum bivariate PBS"
+    if BORROW_PROPAGATED * msg + BORROW_PROPAGATED >= total:
+        # the prefix sum packs left borrow state * message_modulus + right borrow state
+        return "two borrow states packed for the prefix-sum bivariate PBS overflow the block"
+    return None
+
+
+def div_refusal(msg: int, carry: int):
+    """Why the unsigned long division (div_mod.rs:92-492) cannot serve a modulus pair (None: it can): the
+    conditions its own arithmetic needs, each stated where it is used in _unchecked_div_rem."""
+    total = msg * carry
+    if msg < 2 or msg & (msg - 1):
+        # the loop goes bit by bit and trims the divisor at a bit boundary (div_mod.rs:125-129)
+        return "the message modulus is not a power of two: the loop trims and shifts whole bits"
+    sub = overflowing_sub_refusal(msg, carry)
+    if sub:
+        return sub                                    # the overflowing sub of every iteration
+    if (msg - 1) * msg + (msg - 1) >= total:
+        # R << 1: unchecked_scalar_left_shift packs previous * message_modulus + current (scalar_shift.rs:603-615)
+        return "carry_modulus < message_modulus: two messages packed for the shift's bivariate PBS overflow the block"
+    if 2 * (msg - 1) + msg >= total:
+        # remainder1 + remainder2 - divisor + message_modulus: the degree the bookkeeping gives the difference
+        return "the degree of remainder1 + remainder2 - divisor, 3 * message_modulus - 2, overflows the block"
+    if 3 * (msg - 1) + 2 >= total:
+        # the zero-outs pack block * 3 + overflow_sum, overflow_sum = overflowed + upper blocks non-zero <= 2
+        return "a message packed with factor 3 over the overflow sum (0, 1, 2) overflows the block"
+    if msg + 1 >= total:
+        # merge_overflow_flags packs overflowed * message_modulus + upper blocks non-zero
+        return "the two overflow flags packed for the quotient bit overflow the block"
+    return None
+
+
 IS_INFERIOR, IS_EQUAL, IS_SUPERIOR = 0, 1, 2   # comparator.rs:43-45
 _NEG1 = (1 << 64) - 1
 
@@ -538,6 +653,8 @@ class ServerKey:
         self.bivariate_refusal = bivariate_refusal(m, self.carry)
         self.comparison_refusal = comparison_refusal(m, self.carry)
         self.barrel_shifter_refusal = barrel_shifter_refusal(m, self.carry)
+        self.overflowing_sub_refusal = overflowing_sub_refusal(m, self.carry)
+        self.div_refusal = div_refusal(m, self.carry)
         self.bits = m.bit_length() - 1          # message bits per block
         self._luts = {}   # the LUTs of neg .. min / max, built on first use: (name, ...) -> LookupTable
 
@@ -553,6 +670,11 @@ class ServerKey:
         """generate_lookup_table_bivariate (bivariate_pbs.rs:69-100), left scaling = message modulus."""
         m = self.msg
         return self.shortint.generate_lookup_table(lambda x: f((x // m) % m, (x % m) % m))
+
+    def generate_lookup_table_bivariate_with_factor(self, f, factor: int) -> LookupTable:
+        """bivariate_pbs.rs:71-96: the left operand is scaled by `factor`, not by the message modulus."""
+        m = self.msg
+        return self.shortint.generate_lookup_table(lambda x: f((x // factor) % m, (x % factor) % m))
 
     # -- block primitives (shortint) -----------------------------------------------------------
     def _trivial_pbs(self, rb: RadixBatch, j: int, lut: LookupTable):
@@ -803,12 +925,16 @@ class ServerKey:
     # pack_block_chunk, the LWE subtraction of compare_block_assign, 4 * high + low of the sign tree, the sums
     # of eq / ne, the bivariate packing -- is the prepare op of the request that consumes it.  A BooleanBlock
     # is a one-block RadixBatch of degree <= 1.  Out of scope: signed integers, scalar add / sub / bitwise ops /
-    # comparisons, overflowing sub, div / abs and the smart_* forms.
-    def _lut(self, key, f, bivariate: bool = False) -> LookupTable:
-        """One LookupTable object per function for the life of the key: the device caches go by identity."""
+    # comparisons, signed div / abs and the smart_* forms.
+    def _lut(self, key, f, bivariate: bool = False, factor: int = 0) -> LookupTable:
+        """One LookupTable object per function for the life of the key: the device caches go by identity.  factor:
+        a bivariate LUT whose left operand is scaled by it."""
         t = self._luts.get(key)
         if t is None:
-            t = self.generate_lookup_table_bivariate(f) if bivariate else self.shortint.generate_lookup_table(f)
+            if factor:
+                t = self.generate_lookup_table_bivariate_with_factor(f, factor)
+            else:
+                t = self.generate_lookup_table_bivariate(f) if bivariate else self.shortint.generate_lookup_table(f)
             self._luts[key] = t
         return t
 
@@ -941,22 +1067,43 @@ class ServerKey:
         unchecked_ne_parallelized (comparison.rs:55-83): blocks of 0 / 1 are summed in chunks of
         msg * carry - 1, a LUT tells whether the sum is the chunk's length (eq) or non-zero (ne); one PBS layer
         per pass.  blocks: [(batch, block)]; returns the one-block batch."""
+        layer = _PbsLayer(self)
+        (rb, _), = self._join(layer, self._reduce_block_comparisons_steps(layer, blocks, all_true))
+        assert rb.num_blocks == 1   # one block in, or the single chunk of the last pass
+        return rb
+
+    def _reduce_block_comparisons_steps(self, layer: _PbsLayer, blocks: list, all_true: bool):
+        """The loop of _reduce_block_comparisons as a branch of _join: it queues a pass on `layer` and yields where
+        the reference waits for it.  Returns the (batch, block) left; a single block comes back as it is."""
         count = blocks[0][0].count
         max_value = self.msg * self.carry - 1
         while len(blocks) > 1:
             chunks = [blocks[c:c + max_value] for c in range(0, len(blocks), max_value)]
             out = self._new(count, len(chunks))
-            layer = _PbsLayer(self)
             for c, chunk in enumerate(chunks):
                 n = len(chunk)
                 lut = self._lut(("sum_is", n), lambda x, n=n: int(x == n)) if all_true else \
                     self._lut(("sum_non_zero",), lambda x: int(x != 0))
                 layer.add(out, c, lut, prepare=(0, [(rb, j, 1) for rb, j in chunk]))
-            layer.flush()
+            yield
             blocks = [(out, c) for c in range(len(chunks))]
-        rb, _ = blocks[0]
-        assert rb.num_blocks == 1   # one block in, or the single chunk of the last pass
-        return rb
+        return blocks[0]
+
+    def _join(self, layer: _PbsLayer, *branches) -> list:
+        """rayon::join / par_iter over branches that take several PBS passes each: pass k of every branch goes
+        into the same batched launch.  A branch is a generator that queues its requests on `layer` and yields
+        where it needs them done; what it returns is its result."""
+        results, live = [None] * len(branches), dict(enumerate(branches))
+        while live:
+            for i, branch in list(live.items()):
+                try:
+                    next(branch)
+                except StopIteration as done:
+                    results[i] = done.value
+                    del live[i]
+            if layer.reqs:
+                layer.flush()
+        return results
 
     def _unchecked_equality(self, name: str, lhs: RadixBatch, rhs: RadixBatch) -> RadixBatch:
         self._require(f"unchecked_{name}_parallelized", self.bivariate_refusal)
@@ -1370,6 +1517,302 @@ class ServerKey:
             self.full_propagate(ct)
         self._assign(ct, self._unchecked_scalar_mul(name, ct, scalar))
 
+    # ---- overflowing sub, zero tests, division ------------------------------------------------------------------------
+    # The deepest DAGs of the layer: a division is bits * blocks dependent iterations.  Every PBS layer is a fused
+    # _PbsLayer, and nothing runs between two layers: a radix value is a list of (batch, block) here, so a slice, a
+    # rotation, a prepended block or the carry-over of a prefix-sum step is a list operation, every sum or difference
+    # of blocks is the prepare op of the request that consumes it, and every output goes to a fresh batch (no op of a
+    # block-layer call reads what another writes).  Branches the reference joins run in lockstep through _join and
+    # share their passes.  On the device the tables come from one _LayerPlan per operand shape (_DeviceOps.plan).
+    @staticmethod
+    def _terms(blocks, scalar: int = 1) -> list:
+        return [(rb, j, scalar) for rb, j in blocks]
+
+    @staticmethod
+    def _shape_key(*operands) -> tuple:
+        return tuple((rb.count, tuple(rb.degree), tuple(rb.noise)) for rb in operands)
+
+    def _check_pair(self, name: str, lhs: RadixBatch, rhs: RadixBatch, what=("left", "right")):
+        if lhs.num_blocks != rhs.num_blocks or lhs.num_blocks == 0:
+            raise ValueError(f"integer {name}: the {what[0]} operand has {lhs.num_blocks} blocks and the {what[1]} one "
+                             f"{rhs.num_blocks}; the operands take the same, non-zero block count")
+        if lhs.count != rhs.count:
+            raise ValueError(f"integer {name}: {lhs.count} {what[0]} operands against {rhs.count} {what[1]} ones")
+
+    def _check_clean(self, name: str, *operands):
+        if not all(rb.block_carries_are_empty(self.msg) for rb in operands):
+            raise ValueError(f"integer {name}: the unchecked form takes operands with empty carries")
+
+    # -- overflowing sub ------------------------------------------------------------------------------------------------
+    def _borrow_luts(self):
+        """generate_init_borrow_array's two LUTs (sub.rs:687-705): the first block generates a borrow or not, the
+        others may also propagate one"""
+        m = self.msg
+        return (self._lut(("borrow_init", "first"), lambda x: BORROW_GENERATED if x < m else BORROW_NONE),
+                self._lut(("borrow_init",), lambda x: BORROW_GENERATED if x < m else
+                          (BORROW_PROPAGATED if x == m else BORROW_NONE)))
+
+    def _overflowing_sub_steps(self, layer: _PbsLayer, count: int, lhs: list, rhs: list):
+        """unchecked_unsigned_overflowing_sub_parallelized (sub.rs:355-421) as a branch of _join.  lhs: per block
+        the [(batch, block)] whose sum is the block (the division hands remainder1 + remainder2 over unsummed); rhs:
+        [(batch, block)].  Returns ([(batch, block)] of the difference, (batch, 0) of the output borrow, a one-block
+        batch of degree 1).
+
+        Block j of shortint unchecked_sub is lhs_j - rhs_j + z * delta, z = max(ceil(degree(rhs_j) / msg), 1) * msg
+        (neg.rs:223-246): in msg .. 2 msg - 1 where the block needs no borrow, below msg where it does.  It is never
+        stored: it is the prepare op of generate_init_borrow_array's LUT and, with the input borrow subtracted as a
+        fourth term (the true LWE subtraction of sub.rs:410-414), of the closing message_extract.  The prefix sum
+        (compute_borrow_propagation_parallelized_low_latency, sub.rs:727-765, over compute_prefix_sum_hillis_steele,
+        add.rs:572-603) packs state_b * msg + state_(b - space) in the prepare op of its LUT and writes a fresh batch
+        per step; a state that a step does not touch stays where it is.  The top state has a batch of its own in every
+        step, so the output borrow is a whole batch."""
+        m, nb, delta, total = self.msg, len(rhs), self.p.delta, self.msg * self.carry
+        assert nb > 0 and len(lhs) == nb
+
+        def difference(j, extra=()):
+            z = max(-(-rhs[j][0].degree[rhs[j][1]] // m), 1) * m
+            if sum(rb.degree[i] for rb, i in lhs[j]) + z >= total:       # overflowing_sub_refusal: carry >= 2
+                raise ValueError(f"unsigned_overflowing_sub: block {j} of the difference overflows the block")
+            return z * delta, self._terms(lhs[j]) + [(rhs[j][0], rhs[j][1], -1)] + list(extra)
+
+        def fresh(first, last):
+            """places of the states first .. last (last: the top one, in a batch of its own)"""
+            low = self._new(count, last - first) if last > first else None
+            return [(low, b - first) for b in range(first, last)] + [(self._new(count, 1), 0)]
+
+        first_lut, other_lut = self._borrow_luts()
+        states = fresh(0, nb - 1)
+        for b, (rb, j) in enumerate(states):
+            layer.add(rb, j, first_lut if b == 0 else other_lut, prepare=difference(b))
+        yield
+        space = 1
+        for _ in range((nb - 1).bit_length()):                           # ceil_ilog2(nb) steps
+            step = states[:space] + fresh(space, nb - 1)
+            for b in range(space, nb):
+                (hi, hj), (lo, lj) = states[b], states[b - space]
+                # overflowing_sub_refusal: the borrow states fit the message bits, two of them the block
+                assert lo.degree[lj] + 1 <= m and hi.degree[hj] * m + lo.degree[lj] < total
+                layer.add(*step[b], self.lut_prefix, prepare=(0, [(hi, hj, m), (lo, lj, 1)]))
+            yield
+            states, space = step, space * 2
+        res = self._new(count, nb)
+        for j in range(nb):          # block j takes the output borrow of block j - 1, block 0 a trivial zero: no term
+            layer.add(res, j, self.lut_message, prepare=difference(j, self._terms(states[j - 1:j] if j else [], -1)))
+        yield
+        out, oj = states[nb - 1]
+        out.degree[oj] = 1           # a boolean, though the LUT that made it has degree 2 (sub.rs:418-421)
+        return [(res, j) for j in range(nb)], (out, oj)
+
+    def unchecked_unsigned_overflowing_sub_parallelized(self, lhs: RadixBatch, rhs: RadixBatch):
+        """sub.rs:355-381: (lhs - rhs modulo msg ** blocks, lhs < rhs as a one-block batch of degree 1)."""
+        name = "unchecked_unsigned_overflowing_sub_parallelized"
+        self._require(name, self.overflowing_sub_refusal)
+        self._check_pair(name, lhs, rhs)
+        self._check_clean(name, lhs, rhs)
+        lhs, rhs = self._resident(lhs), self._resident(rhs)
+        nb = lhs.num_blocks
+        with self.ops.plan(("overflowing_sub",) + self._shape_key(lhs, rhs),
+                           list(self._borrow_luts()) + [self.lut_prefix, self.lut_message]):
+            layer = _PbsLayer(self)
+            (res, (borrow, _)), = self._join(layer, self._overflowing_sub_steps(
+                layer, lhs.count, [[(lhs, j)] for j in range(nb)], [(rhs, j) for j in range(nb)]))
+        return res[0][0], borrow
+
+    def unsigned_overflowing_sub_parallelized(self, lhs: RadixBatch, rhs: RadixBatch):
+        """sub.rs:318-353."""
+        name = "unsigned_overflowing_sub_parallelized"
+        self._require(name, self.overflowing_sub_refusal)
+        self._check_pair(name, lhs, rhs)
+        return self.unchecked_unsigned_overflowing_sub_parallelized(self._clean(lhs), self._clean(rhs))
+
+    # -- zero tests -----------------------------------------------------------------------------------------------------
+    def _compare_blocks_with_zero_steps(self, layer: _PbsLayer, blocks: list, equality: bool):
+        """compare_blocks_with_zero (scalar_comparison.rs:254-296) as a branch of _join: blocks with empty carries are
+        summed in chunks of (msg * carry - 1) // (msg - 1), one LUT per chunk tells whether the sum is zero (equality)
+        or not.  blocks: [(batch, block)]; returns [(batch, block)] of 0 / 1, empty for no blocks."""
+        if not blocks:
+            return []
+        total = self.msg * self.carry
+        assert all(rb.degree[j] < self.msg for rb, j in blocks)
+        fill = (total - 1) // (self.msg - 1)
+        chunks = [blocks[c:c + fill] for c in range(0, len(blocks), fill)]
+        out = self._new(blocks[0][0].count, len(chunks))
+        lut = self._lut(("sum_is_zero",), lambda x: int(x % total == 0)) if equality else \
+            self._lut(("sum_non_zero",), lambda x: int(x != 0))
+        for c, chunk in enumerate(chunks):
+            layer.add(out, c, lut, prepare=(0, self._terms(chunk)))
+        yield
+        return [(out, c) for c in range(len(chunks))]
+
+    def _comparisons_block_true_steps(self, layer: _PbsLayer, count: int, blocks: list, all_true: bool):
+        """are_all_comparisons_block_true / is_at_least_one_comparisons_block_true (scalar_comparison.rs:147-233) as a
+        branch of _join: no block gives a trivial 1, one block comes back as it is, without a PBS."""
+        if not blocks:
+            one = self.create_trivial_zero(count, 1)
+            self.ops.block_layer([(self.ops.block(one, 0), self.p.delta, [])])
+            one.degree[0] = 1
+            return one, 0
+        return (yield from self._reduce_block_comparisons_steps(layer, blocks, all_true))
+
+    def _are_all_comparisons_block_true_steps(self, layer: _PbsLayer, count: int, blocks: list):
+        return self._comparisons_block_true_steps(layer, count, blocks, True)
+
+    def _is_at_least_one_comparisons_block_true_steps(self, layer: _PbsLayer, count: int, blocks: list):
+        return self._comparisons_block_true_steps(layer, count, blocks, False)
+
+    # -- division -------------------------------------------------------------------------------------------------------
+    def _div_luts(self) -> dict:
+        """Every LUT a division can ask for, by role, in a fixed order: the one stack of its table plan."""
+        m, bits = self.msg, self.bits
+        first, other = self._borrow_luts()
+        window, end = self._scalar_shift_luts("left_shift", 1)
+        luts = {"borrow_first": first, "borrow": other, "prefix": self.lut_prefix, "message": self.lut_message,
+                "shift": window, "shift_end": end, "non_zero": self._lut(("sum_non_zero",), lambda x: int(x != 0))}
+        for pos in range(bits - 1):       # the trims at bit pos of a block (div_mod.rs:209-269)
+            keep, drop = (m - 1) >> (bits - (pos + 1)), ((m - 1) << (pos + 1)) & (m - 1)
+            luts["keep", pos] = self._lut(("mask", keep), lambda x, k=keep: x & k)
+            luts["drop", pos] = self._lut(("mask", drop), lambda x, k=drop: x & k)
+        for factor in (2, 3):             # overflow_sum.degree + 1: without and with upper divisor blocks
+            for name, zero_when in (("zero_unless_overflow", lambda s: s == 0), ("zero_if_overflow", lambda s: s != 0)):
+                luts[name, factor] = self._lut(("div", name, factor), lambda block, s, z=zero_when: 0 if z(s) else block,
+                                               factor=factor)
+        for pos in range(bits):           # merge_overflow_flags_luts (div_mod.rs:167-173)
+            luts["quotient_bit", pos] = self._lut(("div", "quotient_bit", pos),
+                                                  lambda x, y, p=pos: int(x == 0 and y == 0) << p, bivariate=True)
+        return luts
+
+    def _unchecked_div_rem(self, numerator: RadixBatch, divisor: RadixBatch):
+        """unsigned_unchecked_div_rem_parallelized (div_mod.rs:92-492): the long division, most significant bit
+        first.  One iteration at live width L (the blocks of the remainder that can be non-zero) is
+          one pass: the two trims of the divisor at the bit boundary and R << 1 of remainder1 (with the numerator
+            block prepended: a list insert, the block is the source of the shift's first terms) and of remainder2;
+          max(2 + ceil(log2 L), depth of the zero test) passes, joined: the overflowing sub of remainder1 + remainder2
+            and the live divisor blocks, the zero test of the divisor's upper blocks, the cleaned merged remainder;
+          one pass: the two conditional zero-outs, with factor = overflow_sum.degree + 1, and the quotient bit.
+        A last pass cleans quotient and remainder.  Returns (quotient, remainder), fresh batches.
+
+        Quotient block j is the sum of its bits' blocks (the reference adds each to the block as it is made); the
+        sum is the prepare op of the block's closing message_extract.  The numerator block that has given its last
+        bit is shifted once more and dropped, as in the reference, and its PBS counted."""
+        K, nb, bits, m, total = numerator.count, numerator.num_blocks, self.bits, self.msg, self.msg * self.carry
+        lut = self._div_luts()
+        with self.ops.plan(("div_rem",) + self._shape_key(numerator, divisor), list(lut.values())):
+            zero = self.create_trivial_zero(K, 1)
+            remainder1, remainder2 = [(zero, 0)] * nb, [(zero, 0)] * nb
+            numerator_block_stack = [(numerator, j) for j in range(nb)]
+            quotient_bits = [[] for _ in range(nb)]
+            layer = _PbsLayer(self)
+            for i in reversed(range(bits * nb)):
+                block_of_bit, pos_in_block = divmod(i, bits)
+                msb_bit_set = bits * nb - 1 - i
+                live = msb_bit_set // bits + 1                           # last_non_trivial_block + 1
+                interesting_divisor = [(divisor, j) for j in range(live)]
+                divisor_ms_blocks = [(divisor, j) for j in range((msb_bit_set + 1) // bits, nb)]
+                # -- pass 1: trims and shifts
+                if (msb_bit_set + 1) % bits:
+                    pos, trimmed = msb_bit_set % bits, self._new(K, 2)
+                    layer.add(trimmed, 0, lut["keep", pos], prepare=(0, self._terms(interesting_divisor[-1:])))
+                    interesting_divisor[-1] = (trimmed, 0)
+                    if divisor_ms_blocks:
+                        layer.add(trimmed, 1, lut["drop", pos], prepare=(0, self._terms(divisor_ms_blocks[:1])))
+                        divisor_ms_blocks[0] = (trimmed, 1)
+                shifted = []
+                for blocks in ([numerator_block_stack.pop()] + remainder1[:live], remainder2[:live]):
+                    assert all(rb.degree[j] < m for rb, j in blocks)     # div_refusal: two messages fit a block
+                    out = self._new(K, len(blocks))
+                    layer.add(out, 0, lut["shift_end"], prepare=(0, self._terms(blocks[:1])))
+                    for j in range(1, len(blocks)):                      # previous * msg + current
+                        layer.add(out, j, lut["shift"],
+                                  prepare=(0, self._terms(blocks[j - 1:j], m) + self._terms(blocks[j:j + 1])))
+                    shifted.append([(out, j) for j in range(len(blocks))])
+                layer.flush()
+                if pos_in_block != 0:                                    # bits left in the numerator block
+                    numerator_block_stack.append(shifted[0][0])
+                merged = [[a, b] for a, b in zip(shifted[0][1:], shifted[1])]   # remainder1 + remainder2, unsummed
+
+                # -- joined passes: overflowing sub | upper blocks of the divisor != 0 | clean merged remainder
+                def check_divisor_upper_blocks():
+                    if not divisor_ms_blocks:
+                        return None                                      # a trivial zero: no term below
+                    tmp = yield from self._compare_blocks_with_zero_steps(layer, divisor_ms_blocks, False)
+                    return (yield from self._is_at_least_one_comparisons_block_true_steps(layer, K, tmp))
+
+                def create_clean_version_of_merged_remainder():
+                    out = self._new(K, live)
+                    for j in range(live):
+                        layer.add(out, j, lut["message"], prepare=(0, self._terms(merged[j])))
+                    yield
+                    return [(out, j) for j in range(live)]
+
+                (new_remainder, overflowed), upper_non_zero, cleaned = self._join(
+                    layer, self._overflowing_sub_steps(layer, K, merged, interesting_divisor),
+                    check_divisor_upper_blocks(), create_clean_version_of_merged_remainder())
+                # -- last pass: zero-outs and quotient bit
+                flags = [overflowed] + ([upper_non_zero] if upper_non_zero else [])
+                overflow_sum_degree = sum(rb.degree[j] for rb, j in flags)
+                assert overflow_sum_degree <= 2
+                factor = overflow_sum_degree + 1
+                assert (m - 1) * factor + overflow_sum_degree < total   # div_refusal: the factor-3 packing
+                kept1, kept2, bit = self._new(K, live), self._new(K, live), self._new(K, 1)
+                for j in range(live):
+                    layer.add(kept1, j, lut["zero_unless_overflow", factor],
+                              prepare=(0, self._terms(cleaned[j:j + 1], factor) + self._terms(flags)))
+                    layer.add(kept2, j, lut["zero_if_overflow", factor],
+                              prepare=(0, self._terms(new_remainder[j:j + 1], factor) + self._terms(flags)))
+                layer.add(bit, 0, lut["quotient_bit", pos_in_block],
+                          prepare=(0, self._terms(flags[:1], m) + self._terms(flags[1:])))
+                layer.flush()
+                remainder1[:live] = [(kept1, j) for j in range(live)]
+                remainder2[:live] = [(kept2, j) for j in range(live)]
+                quotient_bits[block_of_bit].append((bit, 0))
+            quotient, remainder = self._new(K, nb), self._new(K, nb)
+            for j in range(nb):
+                layer.add(remainder, j, lut["message"], prepare=(0, self._terms([remainder1[j], remainder2[j]])))
+                layer.add(quotient, j, lut["message"], prepare=(0, self._terms(quotient_bits[j])))
+            layer.flush()
+        return quotient, remainder
+
+    def _div_rem(self, name: str, numerator: RadixBatch, divisor: RadixBatch, unchecked: bool, assign: bool):
+        """The preamble of every division entry point (div_mod.rs:597-631, 656-864): refusal and shape checks before
+        the first launch; the default forms propagate whichever operand has carries, the divisor on a clone, the
+        numerator itself in an _assign form and on a clone otherwise."""
+        self._require(name, self.div_refusal)
+        self._check_pair(name, numerator, divisor, ("numerator", "divisor"))
+        if unchecked:
+            self._check_clean(name, numerator, divisor)
+            return self._unchecked_div_rem(self._resident(numerator), self._resident(divisor))
+        divisor = self._clean(divisor)
+        if assign and not numerator.block_carries_are_empty(self.msg):
+            self.full_propagate(numerator)
+        return self._unchecked_div_rem(self._clean(numerator), divisor)
+
+    def unchecked_div_rem_parallelized(self, numerator: RadixBatch, divisor: RadixBatch):
+        """div_mod.rs:92-492 (unsigned): (quotient, remainder); a zero divisor gives (2^T - 1, numerator)."""
+        return self._div_rem("unchecked_div_rem_parallelized", numerator, divisor, True, False)
+
+    def div_rem_parallelized(self, numerator: RadixBatch, divisor: RadixBatch):
+        """div_mod.rs:597-631."""
+        return self._div_rem("div_rem_parallelized", numerator, divisor, False, False)
+
+
+def _add_div_methods():
+    """the eight div / rem forms over div_rem (div_mod.rs:656-864)"""
+    def form(which, unchecked, assign):
+        def f(self, numerator, divisor):
+            res = self._div_rem(f.__name__, numerator, divisor, unchecked, assign)[which]
+            if not assign:
+                return res
+            self._assign(numerator, res)
+        return f
+
+    for which, op in enumerate(("div", "rem")):
+        for unchecked in (True, False):
+            for assign in (True, False):
+                f = form(which, unchecked, assign)
+                name = f"{'unchecked_' if unchecked else ''}{op}{'_assign' if assign else ''}_parallelized"
+                f.__name__ = f.__qualname__ = name
+                setattr(ServerKey, name, f)
+
 
 def _add_shift_methods():
     """the public names of the sixteen scalar and the sixteen encrypted forms"""
@@ -1409,6 +1852,7 @@ def _add_shift_methods():
 
 
 _add_shift_methods()
+_add_div_methods()
 
 
 # ---- integer WoP-PBS (integer/wopbs/mod.rs) ----------------------------------------------------------
