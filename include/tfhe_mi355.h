@@ -728,6 +728,14 @@ int tfhe_mi355_fill_accumulator(const TfheMi355Parameters *params, const uint64_
  * acc_inout[i] += X_i and set_out[i] = X_i, X_i = rint_half_even(fr[i] * 2^64) mod 2^64. */
 int tfhe_mi355_debug_torus_from_fraction(int device, const double *fr, uint64_t *acc_inout, uint64_t *set_out,
                                          size_t n);
+/* Diagnostic: workgroups of the classic u64 PBS kernel of the context's shape resident at once -- the size of
+ * its persistent grid, whose slots take further ciphertexts from a ticket (a workgroup holds 4 ciphertexts at
+ * N = 2048, k = 1, level 1, otherwise 1); 0 for a shape without a persistent grid.  rc 1 on a context the
+ * kernel does not serve (N >= 4096, multi-bit, keys of another torus width).
+ * TFHE_MI355_GRID_CAP=<n>, read at every launch, caps that grid, the grid of the AES mask stream of the seeded
+ * uploads and expansions, and the row grids of tfhe_mi355_lwe_expand (a test hook: the loops that walk the work
+ * beyond the grid then wrap at small counts; unset or 0: no cap; the query above reports the uncapped grid). */
+int tfhe_mi355_debug_pbs_resident(TfheMi355Context *ctx, size_t *count);
 
 /* ---- 32-bit torus (the reference's boolean module, tfhe/src/boolean) ----
  * The boolean engine computes on LweCiphertextOwned<u32> under a LweKeyswitchKeyOwned<u32> and the Fourier

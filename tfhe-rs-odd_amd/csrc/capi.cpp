@@ -3261,6 +3261,21 @@ int tfhe_mi355_debug_torus_from_fraction(int device, const double *fr, uint64_t 
     });
 }
 
+int tfhe_mi355_debug_pbs_resident(TfheMi355Context *ctx, size_t *count) {
+    return guarded([&] {
+        ctx = primary(ctx);  // every shard has the same shape; the first device answers
+        if (!ctx || !count) fail("null argument");
+        require_width64(ctx);
+        const TfheMi355Parameters &p = ctx->p;
+        if (p.grouping_factor || is_large(ctx) ||
+            !classic_pbs_supported((int)p.polynomial_size, (int)p.glwe_dimension, (int)p.pbs_level))
+            fail("no classic 64-bit-torus PBS kernel for N=%u k=%u pbs_level=%u grouping_factor=%u", p.polynomial_size,
+                 p.glwe_dimension, p.pbs_level, p.grouping_factor);
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        *count = (size_t)classic_pbs_resident_blocks((int)ctx->N(), (int)ctx->k(), (int)p.pbs_level);
+    });
+}
+
 int tfhe_mi355_fill_accumulator(const TfheMi355Parameters *params, const uint64_t *f_values, uint64_t *acc) {
     return guarded([&] {
         if (!params || !f_values || !acc) fail("null argument");

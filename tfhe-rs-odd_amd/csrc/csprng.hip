@@ -79,7 +79,7 @@ hipError_t launch_seeded_decompress_from(const void *d_tables, const uint64_t *d
     if (words) {
         const size_t first = first_row * row_words;
         const size_t blocks = (first + words + 1) / 2 - first / 2 + 1;
-        const unsigned grid = (unsigned)std::min<size_t>((blocks + 255) / 256, 65536);
+        const unsigned grid = (unsigned)std::min(std::min<size_t>((blocks + 255) / 256, 65536), grid_cap());
         hipLaunchKernelGGL(csprng_mask_kernel, dim3(grid), dim3(256), 0, s,
                            reinterpret_cast<const AesTables *>(d_tables), first, words, row_words, stride,
                            reinterpret_cast<uint8_t *>(d_out));

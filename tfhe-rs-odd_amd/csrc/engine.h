@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -117,6 +118,16 @@ struct TimedLaunch {
     }
 };
 
+// test hook: TFHE_MI355_GRID_CAP=<n>, read at every launch, caps the workgroups of the launches whose grid is
+// capped already and whose kernel walks the rest of the work in a loop -- the persistent grid of the classic PBS
+// (pbs_classic.hip), the AES mask stream (csprng.hip) and the ingress row kernels (lwe_ingress.hip) -- so that
+// the loop wraps at small counts (unset or 0: no cap; the GGSW launches have TFHE_MI355_GGSW_GRID)
+inline size_t grid_cap() {
+    const char *e = std::getenv("TFHE_MI355_GRID_CAP");
+    const long v = e && *e ? std::atol(e) : 0;
+    return v > 0 ? (size_t)v : ~(size_t)0;
+}
+
 struct FftTables {
     // device tables, M entries each (M = N/2)
     double2 *W = nullptr;          // exp(-2 pi i t / M)
@@ -145,6 +156,9 @@ struct ClassicPbsLaunch {
 bool classic_pbs_supported(int N, int k, int L);
 // device scratch (zeroed by the caller before each launch) for the persistent grid's ticket
 size_t classic_pbs_ticket_bytes(int N, int k, int L);
+// workgroups of the shape's kernel resident at once on the current device: the persistent grid's size before
+// grid_cap() (0: the shape has no persistent grid, or no kernel)
+int classic_pbs_resident_blocks(int N, int k, int L);
 hipError_t launch_classic_pbs(int N, int k, int L, const ClassicPbsLaunch &a, hipStream_t s);
 // latency form (pbs_latency.hip): one ciphertext per workgroup of 8 waves, same outputs; for small
 // batches (the one-ciphertext-per-call pattern).  N = 2048, k = 1, L = 1 only; no ticket, no scratch.

@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) lwe_compact_expand_kernel(const uint64_t 
 hipError_t launch_lwe_compact_expand(const uint64_t *d_masks, const uint64_t *d_bodies, size_t n, size_t first,
                                      size_t count, uint64_t *d_out, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>(count, (size_t)1 << 20);
+    const unsigned grid = (unsigned)std::min(std::min<size_t>(count, (size_t)1 << 20), grid_cap());
     hipLaunchKernelGGL(lwe_compact_expand_kernel, dim3(grid), dim3(256), 0, s, d_masks, d_bodies, n, first, count,
                        d_out);
     return hipGetLastError();
@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(256) csprng_rows_kernel(const AesTables *__res
 hipError_t launch_csprng_rows(const void *d_base_tables, const uint64_t *d_seeds, const uint64_t *d_bodies, size_t n,
                               size_t count, uint64_t *d_out, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>(count, (size_t)1 << 20);
+    const unsigned grid = (unsigned)std::min(std::min<size_t>(count, (size_t)1 << 20), grid_cap());
     hipLaunchKernelGGL(csprng_rows_kernel, dim3(grid), dim3(256), 0, s,
                        reinterpret_cast<const AesTables *>(d_base_tables), d_seeds, d_bodies, n, count, d_out);
     return hipGetLastError();

@@ -393,7 +393,9 @@ static hipError_t launch_pbs_t(const ClassicPbsLaunch &a, hipStream_t s) {
     const int threads = 64 * (K + 1) * CPW;
     int blocks = (a.count + CPW - 1) / CPW;
     if (PbsConfig<N, K, L>::PERSIST && a.ticket) {
-        const int res = resident_blocks((const void *)pbs_classic_kernel<N, K, L>, threads, lds);
+        // (grid_cap(): the test hook of engine.h; a small cap leads to the ticketed launch below)
+        const int res = (int)std::min<size_t>(
+            (size_t)resident_blocks((const void *)pbs_classic_kernel<N, K, L>, threads, lds), grid_cap());
         if (CPW > 1 && a.count <= res * (CPW - 1)) {
             // fewer ciphertexts than a packed resident grid: spread them, ceil(count / res) per
             // workgroup (latency of the coalesced small batches: 9.0 -> 5.8 ms at 2_2 alone on a CU)
@@ -427,6 +429,18 @@ size_t classic_pbs_ticket_bytes(int N, int k, int L) {
 #define PBS_TICKET(n_, k_, l_) if (N == n_ && k == k_ && L == l_) return PbsConfig<n_, k_, l_>::PERSIST ? 256 : 0;
     PBS_CLASSIC_SHAPES(PBS_TICKET)
 #undef PBS_TICKET
+    return 0;
+}
+
+int classic_pbs_resident_blocks(int N, int k, int L) {
+#define PBS_RESIDENT(n_, k_, l_)                                                                           \
+    if (N == n_ && k == k_ && L == l_)                                                                     \
+        return !PbsConfig<n_, k_, l_>::PERSIST                                                             \
+                   ? 0                                                                                     \
+                   : resident_blocks((const void *)pbs_classic_kernel<n_, k_, l_>,                         \
+                                     64 * (k_ + 1) * PbsConfig<n_, k_, l_>::CPW, PbsConfig<n_, k_, l_>::lds_bytes());
+    PBS_CLASSIC_SHAPES(PBS_RESIDENT)
+#undef PBS_RESIDENT
     return 0;
 }
 

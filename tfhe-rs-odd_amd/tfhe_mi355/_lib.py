@@ -235,6 +235,7 @@ SIGNATURES = [
      [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, sz, ctypes.c_double, u64p]),
     ("tfhe_mi355_debug_torus_from_fraction", ctypes.c_int,
      [ctypes.c_int, ctypes.POINTER(ctypes.c_double), u64p, u64p, sz]),
+    ("tfhe_mi355_debug_pbs_resident", ctypes.c_int, [vp, ctypes.POINTER(sz)]),
     ("tfhe_mi355_client_gen_seeded_bootstrap_key", ctypes.c_int,
      [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, u64p, ctypes.c_uint32]),

@@ -887,6 +887,13 @@ class Engine:
         _lib.call(fn, self._h, count, ctypes.byref(b))
         return b.value
 
+    def pbs_resident(self) -> int:
+        """Workgroups of the classic u64 PBS kernel resident at once on the device: its persistent grid
+        (0: the shape has none)."""
+        n = sz()
+        _lib.call("tfhe_mi355_debug_pbs_resident", self._h, ctypes.byref(n))
+        return n.value
+
     def pbs_scratch_bytes(self, count: int) -> int:
         return self._scratch_query("tfhe_mi355_programmable_bootstrap_scratch", count)
 
