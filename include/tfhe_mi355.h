@@ -712,6 +712,36 @@ typedef struct {
 } TfheMi355BlockOp;
 int tfhe_mi355_lwe_block_layer_async(TfheMi355Context *ctx, const TfheMi355BlockOp *ops, size_t n_ops,
                                      size_t rows, size_t words, void *stream);
+/* The block layer with one clear digit per row.  A clear (unencrypted) operand of a radix operation reaches a
+ * PBS layer in one of two ways: as a plaintext on the body of a block (scalar_add / scalar_sub add the scalar's
+ * digit times delta, radix/scalar_add.rs:53-65; the order comparisons subtract the packed digit before the sign
+ * LUT, comparator.rs:226-238) or as the choice of a LUT out of a small family (x & s, x == s:
+ * radix_parallel/scalar_bitwise_op.rs, scalar_comparison.rs:312-336).  This call reads the operand of row r from
+ * a device array, so the op table does not depend on it: one table, and one captured graph of it, serves another
+ * clear operand in every row and on every replay.  For every op, every row r < rows and every word w < words
+ *   c        = d_clear ? (clear_negate ? (0 - d_clear[r]) mod 2^64 : d_clear[r]) : 0
+ *   digit(r) = (c >> clear_shift) & (2^clear_bits - 1)        (bits past bit 63 read as 0; clear_bits == 0: 0)
+ *   dst[r][w] = sum over the present terms of scalar * src[r][w]
+ *               + (w == words - 1 ? body_add + digit(r) * clear_scale : 0)                   wrapping mod 2^64
+ *   d_lut_index[r] = lut_base + digit(r)     where d_lut_index != NULL, written exactly once per row.
+ * With d_clear == NULL the op is the plain one.  `op`, the aliasing rule, the refusals and the empty calls are
+ * those of tfhe_mi355_lwe_block_layer_async; d_clear and d_lut_index overlap no destination.  Also refused
+ * (rc 1): clear_shift > 63, clear_bits > 8, d_lut_index != NULL with d_clear == NULL and clear_bits != 0.
+ * `ops` is host memory, read before the call returns (about 25 ops per launch travel in the kernel arguments;
+ * longer lists take several launches on the stream).  The call needs no scratch, does not allocate, synchronise
+ * or copy, and can be captured into a hipGraph. */
+typedef struct {
+    TfheMi355BlockOp op;
+    const uint64_t *d_clear; /* device, one u64 per row; NULL: a plain op */
+    uint64_t clear_scale;    /* digit(r) * clear_scale is added to the body of row r */
+    uint32_t *d_lut_index;   /* device, one u32 per row, or NULL */
+    uint32_t clear_negate;   /* 1: the digit comes from (0 - d_clear[r]) mod 2^64 */
+    uint32_t clear_shift;    /* <= 63 */
+    uint32_t clear_bits;     /* 0 .. 8 */
+    uint32_t lut_base;
+} TfheMi355ClearBlockOp;
+int tfhe_mi355_lwe_clear_block_layer_async(TfheMi355Context *ctx, const TfheMi355ClearBlockOp *ops, size_t n_ops,
+                                           size_t rows, size_t words, void *stream);
 /* trivial_pbs_assign (shortint/server_key/mod.rs:763-781) on the bodies of `rows` trivial
  * ciphertexts (d_body points at the first body, rows `stride` words apart) with the GLWE
  * accumulator d_lut ((k+1)*N words, device). */

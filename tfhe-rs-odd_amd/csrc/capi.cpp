@@ -3221,6 +3221,44 @@ int tfhe_mi355_lwe_block_layer_async(TfheMi355Context *ctx, const TfheMi355Block
     });
 }
 
+static_assert(sizeof(TfheMi355ClearBlockOp) == sizeof(ClearBlockLayerOp) &&
+                  offsetof(TfheMi355ClearBlockOp, op) == offsetof(ClearBlockLayerOp, op) &&
+                  offsetof(TfheMi355ClearBlockOp, d_clear) == offsetof(ClearBlockLayerOp, d_clear) &&
+                  offsetof(TfheMi355ClearBlockOp, clear_scale) == offsetof(ClearBlockLayerOp, clear_scale) &&
+                  offsetof(TfheMi355ClearBlockOp, d_lut_index) == offsetof(ClearBlockLayerOp, d_lut_index) &&
+                  offsetof(TfheMi355ClearBlockOp, clear_negate) == offsetof(ClearBlockLayerOp, clear_negate) &&
+                  offsetof(TfheMi355ClearBlockOp, clear_shift) == offsetof(ClearBlockLayerOp, clear_shift) &&
+                  offsetof(TfheMi355ClearBlockOp, clear_bits) == offsetof(ClearBlockLayerOp, clear_bits) &&
+                  offsetof(TfheMi355ClearBlockOp, lut_base) == offsetof(ClearBlockLayerOp, lut_base),
+              "TfheMi355ClearBlockOp and the launcher's ClearBlockLayerOp are one layout");
+
+int tfhe_mi355_lwe_clear_block_layer_async(TfheMi355Context *ctx, const TfheMi355ClearBlockOp *ops, size_t n_ops,
+                                           size_t rows, size_t words, void *stream) {
+    return guarded([&] {
+        ctx = primary(ctx);  // device pointers: the first device's shard
+        if (!ctx || (!ops && n_ops)) fail("null argument");
+        if (n_ops && words == 0) fail("block layer: rows of zero words");
+        for (size_t i = 0; i < n_ops; i++) {
+            const TfheMi355BlockOp &op = ops[i].op;
+            if (!op.dst) fail("block layer: op %zu has a null destination", i);
+            if (op.dst_stride < words) fail("block layer: op %zu: destination row stride smaller than the row", i);
+            for (int t = 0; t < TFHE_MI355_BLOCK_OP_TERMS; t++)
+                if (op.term[t].src && op.term[t].stride < words)
+                    fail("block layer: op %zu term %d: row stride smaller than the row", i, t);
+            if (ops[i].clear_shift > 63) fail("block layer: op %zu: clear_shift %u above 63", i, ops[i].clear_shift);
+            if (ops[i].clear_bits > (uint32_t)CLEAR_BLOCK_LAYER_MAX_BITS)
+                fail("block layer: op %zu: clear_bits %u above %d", i, ops[i].clear_bits, CLEAR_BLOCK_LAYER_MAX_BITS);
+            if (ops[i].d_lut_index && !ops[i].d_clear && ops[i].clear_bits)
+                fail("block layer: op %zu: a LUT index from %u clear bits, but no clear operand", i, ops[i].clear_bits);
+        }
+        if (n_ops == 0 || rows == 0) return;
+        check(hipSetDevice(ctx->device), "hipSetDevice");
+        check(launch_lwe_clear_block_layer(reinterpret_cast<const ClearBlockLayerOp *>(ops), n_ops, rows, words,
+                                           (hipStream_t)stream),
+              "lwe clear block layer");
+    });
+}
+
 int tfhe_mi355_trivial_pbs_async(TfheMi355Context *ctx, uint64_t *d_body, size_t rows, size_t stride,
                                  const uint64_t *d_lut, void *stream) {
     return guarded([&] {

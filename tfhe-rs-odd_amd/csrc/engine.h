@@ -324,6 +324,29 @@ struct BlockLayerOp {
 };
 hipError_t launch_lwe_block_layer(const BlockLayerOp *ops, size_t n_ops, size_t rows, size_t words, hipStream_t s);
 
+// The block layer with a clear digit per row (lwe_ops.hip lwe_clear_block_layer_kernel): the plain op, and per row
+//   digit(r) = ((negate ? 0 - d_clear[r] : d_clear[r]) >> clear_shift) & (2^clear_bits - 1)    (d_clear == nullptr: 0)
+//   dst[r][words - 1] += digit(r) * clear_scale,   d_lut_index[r] = lut_base + digit(r)        (where not nullptr).
+// A clear operand of a radix op reaches a PBS layer as a plaintext on the body or as the choice of a LUT out of a
+// family; read per row from the device, neither is part of the op table, so one table (and one captured graph of
+// it) serves any clear operands.  The layout is TfheMi355ClearBlockOp's (capi.cpp asserts it).  The entries per
+// launch follow from the entry's size, so the table and the three row counts stay under the 4 KiB of kernel
+// arguments.  No allocation, no copy, no wait; the launcher does not check the fields (the entry point does).
+struct ClearBlockLayerOp {
+    BlockLayerOp op;
+    const uint64_t *d_clear;
+    uint64_t clear_scale;
+    uint32_t *d_lut_index;
+    uint32_t clear_negate;
+    uint32_t clear_shift;
+    uint32_t clear_bits;
+    uint32_t lut_base;
+};
+constexpr int CLEAR_BLOCK_LAYER_MAX_BITS = 8;
+constexpr int CLEAR_BLOCK_LAYER_OPS_PER_LAUNCH = (int)((4096 - 3 * sizeof(uint32_t)) / sizeof(ClearBlockLayerOp));
+hipError_t launch_lwe_clear_block_layer(const ClearBlockLayerOp *ops, size_t n_ops, size_t rows, size_t words,
+                                        hipStream_t s);
+
 // GLWE x plaintext-polynomial products (glwe_ops.hip):
 //   out[c][i] = sum_{j<J} glwe_in[c][j] * polys[i][j]   in (Z/2^64)[X]/(X^N+1), per GLWE polynomial,
 // optionally sample-extracted at degree 0.  Serves the fork's MVB products v0 * v_i

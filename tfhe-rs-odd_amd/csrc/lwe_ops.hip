@@ -57,6 +57,45 @@ __global__ void __launch_bounds__(256) lwe_block_layer_kernel(const BlockLayerTa
     }
 }
 
+// The block layer with a clear digit per row: lwe_block_layer_kernel's loop, and for the row of the tile
+//   digit = ((negate ? 0 - d_clear[r] : d_clear[r]) >> clear_shift) & (2^clear_bits - 1)
+// times clear_scale on the body, lut_base + digit into d_lut_index[r].  Replaces the plaintext a scalar's digit
+// adds to or subtracts from a block before the LUT (radix/scalar_add.rs:53-65, scalar_sub.rs:109-122,
+// comparator.rs:226-238) and the choice of the LUT by the digit (radix_parallel/scalar_bitwise_op.rs,
+// scalar_comparison.rs:312-336), which the reference does on the host per scalar.  A second kernel, not a
+// template of the first: the plain kernel's code stays as it is.  The row of a tile is the same for the whole
+// workgroup, so d_clear[r] is one uniform load per tile; the lane of w == words - 1 adds the plaintext, lane 0 of
+// the row's first tile (w == 0 < words) stores the index, once per row.
+struct ClearBlockLayerTable {
+    ClearBlockLayerOp op[CLEAR_BLOCK_LAYER_OPS_PER_LAUNCH];
+};
+static_assert(sizeof(ClearBlockLayerTable) + 3 * sizeof(uint32_t) <= 4096, "the table travels in the kernel arguments");
+
+__global__ void __launch_bounds__(256) lwe_clear_block_layer_kernel(const ClearBlockLayerTable table, uint32_t rows,
+                                                                    uint32_t words, uint32_t tiles_per_row) {
+    const ClearBlockLayerOp &c = table.op[blockIdx.y];
+    const BlockLayerOp &op = c.op;
+    const uint32_t tiles = rows * tiles_per_row;
+    const uint64_t mask = ((uint64_t)1 << c.clear_bits) - 1;
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint32_t r = t / tiles_per_row;
+        const uint32_t tile = t - r * tiles_per_row;
+        const uint32_t w = tile * 256 + threadIdx.x;
+        uint64_t digit = 0;
+        if (c.d_clear) {
+            const uint64_t clear = c.d_clear[r];
+            digit = ((c.clear_negate ? 0 - clear : clear) >> c.clear_shift) & mask;
+        }
+        if (c.d_lut_index && tile == 0 && threadIdx.x == 0) c.d_lut_index[r] = c.lut_base + (uint32_t)digit;
+        if (w >= words) continue;
+        uint64_t v = w + 1 == words ? op.body_add + digit * c.clear_scale : 0;
+#pragma unroll
+        for (int i = 0; i < BLOCK_LAYER_TERMS; i++)
+            if (op.term[i].src) v += op.term[i].scalar * op.term[i].src[(size_t)r * op.term[i].stride + w];
+        op.dst[(size_t)r * op.dst_stride + w] = v;
+    }
+}
+
 // trivial ciphertexts (zero mask): body <- LUT body at the box of body / delta (negated past the
 // padding bit); the mask stays zero
 __global__ void __launch_bounds__(256) trivial_pbs_kernel(uint64_t *__restrict__ body, size_t rows, size_t stride,
@@ -206,6 +245,28 @@ hipError_t launch_lwe_block_layer(const BlockLayerOp *ops, size_t n_ops, size_t 
         const size_t per_op = std::max((size_t)1, BLOCK_LAYER_MAX_WORKGROUPS / n);
         hipLaunchKernelGGL(lwe_block_layer_kernel, dim3((unsigned)std::min(tiles, per_op), (unsigned)n), dim3(256), 0, s,
                            table, (uint32_t)rows, (uint32_t)words, (uint32_t)tiles_per_row);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_lwe_clear_block_layer(const ClearBlockLayerOp *ops, size_t n_ops, size_t rows, size_t words,
+                                        hipStream_t s) {
+    if (n_ops == 0 || rows == 0 || words == 0) return hipSuccess;
+    const size_t tiles_per_row = (words + 255) / 256;
+    if (words > 0xFFFFFFFFull || rows > 0xFFFFFFFFull / tiles_per_row) return hipErrorInvalidValue;
+    const size_t tiles = rows * tiles_per_row;
+    // lists longer than one table: several launches, in stream order
+    for (size_t first = 0; first < n_ops; first += CLEAR_BLOCK_LAYER_OPS_PER_LAUNCH) {
+        const size_t n = std::min(n_ops - first, (size_t)CLEAR_BLOCK_LAYER_OPS_PER_LAUNCH);
+        ClearBlockLayerTable table;
+        std::memset(&table, 0, sizeof table);
+        std::memcpy(table.op, ops + first, n * sizeof(ClearBlockLayerOp));
+        // the plain layer's grid: about eight workgroups per compute unit, the grid-stride loop takes the rest
+        const size_t per_op = std::max((size_t)1, BLOCK_LAYER_MAX_WORKGROUPS / n);
+        hipLaunchKernelGGL(lwe_clear_block_layer_kernel, dim3((unsigned)std::min(tiles, per_op), (unsigned)n), dim3(256),
+                           0, s, table, (uint32_t)rows, (uint32_t)words, (uint32_t)tiles_per_row);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

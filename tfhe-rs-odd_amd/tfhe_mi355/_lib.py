@@ -76,6 +76,21 @@ class TfheMi355BlockOp(ctypes.Structure):
     ]
 
 
+class TfheMi355ClearBlockOp(ctypes.Structure):
+    """A block op with a clear digit per row: digit(r) = ((negate ? -d_clear[r] : d_clear[r]) >> clear_shift) &
+    (2^clear_bits - 1); digit * clear_scale goes on the body of row r, lut_base + digit into d_lut_index[r]."""
+    _fields_ = [
+        ("op", TfheMi355BlockOp),
+        ("d_clear", ctypes.c_void_p),
+        ("clear_scale", ctypes.c_uint64),
+        ("d_lut_index", ctypes.c_void_p),
+        ("clear_negate", ctypes.c_uint32),
+        ("clear_shift", ctypes.c_uint32),
+        ("clear_bits", ctypes.c_uint32),
+        ("lut_base", ctypes.c_uint32),
+    ]
+
+
 class TfheMi355CiphertextInfo(ctypes.Structure):
     _fields_ = [
         ("lwe_dimension", ctypes.c_uint32),
@@ -148,6 +163,8 @@ SIGNATURES = [
      [vp, vp, vp, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp]),
     ("tfhe_mi355_lwe_block_layer_async", ctypes.c_int,
      [vp, ctypes.POINTER(TfheMi355BlockOp), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp]),
+    ("tfhe_mi355_lwe_clear_block_layer_async", ctypes.c_int,
+     [vp, ctypes.POINTER(TfheMi355ClearBlockOp), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp]),
     ("tfhe_mi355_trivial_pbs_async", ctypes.c_int, [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp]),
     ("tfhe_mi355_client_gen_multi_bit_bootstrap_key", ctypes.c_int,
      [ctypes.c_uint64, u64p, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,

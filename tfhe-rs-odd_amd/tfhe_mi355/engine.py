@@ -1039,6 +1039,39 @@ class Engine:
         table, n = ops if isinstance(ops, tuple) else self.block_ops(ops)
         _lib.call("tfhe_mi355_lwe_block_layer_async", self._h, table, n, rows, words, _stream_ptr(stream))
 
+    @staticmethod
+    def clear_block_ops(ops):
+        """The C table of a block layer with a clear digit per row, from
+        [(dst_ptr, dst_stride, body_add, terms, clear)]: the first four as block_ops takes them, `clear` None (a
+        plain op) or a dict with any of d_clear (device pointer of one u64 per row), negate, shift, bits, scale,
+        d_lut_index (device pointer of one u32 per row) and lut_base; what is absent is 0 / NULL.  A table can be
+        kept and passed to lwe_clear_block_layer_async again."""
+        table = (_lib.TfheMi355ClearBlockOp * max(len(ops), 1))()
+        for c, (dst, dst_stride, body_add, terms, clear) in zip(table, ops):
+            if len(terms) > _lib.BLOCK_OP_TERMS:
+                raise ValueError(f"a block op takes at most {_lib.BLOCK_OP_TERMS} terms, got {len(terms)}")
+            o = c.op
+            o.dst, o.dst_stride, o.body_add = dst, dst_stride, body_add % (1 << 64)
+            for t, (src, stride, scalar) in zip(o.term, terms):
+                t.src, t.stride, t.scalar = src, stride, scalar % (1 << 64)
+            clear = clear or {}
+            unknown = set(clear) - {"d_clear", "negate", "shift", "bits", "scale", "d_lut_index", "lut_base"}
+            if unknown:
+                raise ValueError(f"unknown fields of a clear block op: {sorted(unknown)}")
+            c.d_clear, c.d_lut_index = clear.get("d_clear"), clear.get("d_lut_index")
+            c.clear_negate, c.clear_shift = int(bool(clear.get("negate", 0))), clear.get("shift", 0)
+            c.clear_bits, c.lut_base = clear.get("bits", 0), clear.get("lut_base", 0)
+            c.clear_scale = clear.get("scale", 0) % (1 << 64)
+        return table, len(ops)
+
+    def lwe_clear_block_layer_async(self, ops, rows: int, words: int, stream=None) -> None:
+        """lwe_block_layer_async with a clear digit per row, read from the device: per op and row r,
+        digit = ((negate ? -d_clear[r] : d_clear[r]) >> shift) & (2^bits - 1); digit * scale is added to the body
+        of row r and lut_base + digit written to d_lut_index[r].  `ops` is a list as clear_block_ops takes it, or
+        what clear_block_ops returned."""
+        table, n = ops if isinstance(ops, tuple) else self.clear_block_ops(ops)
+        _lib.call("tfhe_mi355_lwe_clear_block_layer_async", self._h, table, n, rows, words, _stream_ptr(stream))
+
     def trivial_pbs_async(self, body_ptr: int, rows: int, stride: int, d_lut, stream=None) -> None:
         _lib.call("tfhe_mi355_trivial_pbs_async", self._h, body_ptr, rows, stride, _dev_ptr(d_lut),
                   _stream_ptr(stream))

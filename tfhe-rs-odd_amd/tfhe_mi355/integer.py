@@ -22,6 +22,11 @@ operand pairs at once:
   rotate_right} by an encrypted amount (barrel_shifter), scalar_mul (unchecked and default forms, unsigned)
                                                             radix_parallel/{scalar_shift,scalar_rotate,shift,rotate,
                                                             bit_extractor,scalar_mul}.rs
+  ServerKey scalar_add, scalar_sub, scalar_bit{and,or,xor}, scalar_{eq,ne,gt,ge,lt,le,max,min} (unchecked and default
+  forms, unsigned; one clear operand per batch or per row)
+                                                            radix/scalar_{add,sub}.rs, radix_parallel/scalar_{add,sub,
+                                                            bitwise_op,comparison}.rs, comparator.rs: see "clear
+                                                            operands" in ServerKey
   ServerKey unsigned_overflowing_sub, div_rem, div, rem (unchecked and default forms, unsigned), the zero tests
   compare_blocks_with_zero, is_at_least_one_comparisons_block_true, are_all_comparisons_block_true
                                                             radix_parallel/{sub,div_mod,scalar_comparison}.rs,
@@ -93,6 +98,33 @@ class RadixBatch:
         return self.noise[j] == NOISE_ZERO
 
 
+class _LutFamily:
+    """The LUTs a clear digit chooses from: row r of a request takes luts[digit(r)].  One object per family for the
+    life of the key, as for a LookupTable (the device caches go by identity)."""
+
+    def __init__(self, luts):
+        self.luts = list(luts)
+        self.degree = max(lut.degree for lut in self.luts)
+
+
+class _ClearRows:
+    """One clear operand per row of a batch, as u64: a numpy uint64 array on the host (uploaded once per call on
+    the device path) or a torch int64 tensor on the engine's device (read in place: nothing is copied or checked)."""
+
+    def __init__(self, host=None, dev=None):
+        self.host, self.dev = host, dev
+
+    def on_host(self) -> np.ndarray:
+        if self.host is None:
+            self.host = self.dev.cpu().numpy().view(np.uint64)
+        return self.host
+
+    def on_device(self, ops):
+        if self.dev is None:
+            self.dev = ops.from_host(self.host)
+        return self.dev
+
+
 class _PbsLayer:
     """Collects the independent LUT applications of one DAG layer and runs them in one launch.
 
@@ -102,15 +134,28 @@ class _PbsLayer:
     lands in block j with post_add * delta added to its body (compare_block_assign's + 1).  A layer with such a
     request runs fused (flush_fused): ONE block-layer call assembles the input rows of every request in the
     layer's input buffer, the batched KS+PBS follows, ONE more block-layer call scatters the outputs to their
-    blocks.  Layers without one keep the launch path below, as the multiply DAG pins it."""
+    blocks.  Layers without one keep the launch path below, as the multiply DAG pins it.
+
+    A request may also carry a clear part: one clear operand per row, read on the device (flush_clear).  Between
+    two PBS layers a clear operand is a plaintext on the body of a block or the choice of a LUT out of a family,
+    and the first block-layer call of the layer takes both from the operand of each row, so the DAG and the tables
+    of the layer do not depend on the clear values."""
 
     def __init__(self, sk: "ServerKey"):
         self.sk = sk
-        self.reqs = []  # (batch, block, lut), or with a prepare op (batch, block, lut, body_add, terms, post_add)
+        # (batch, block, lut), with a prepare op (batch, block, lut, body_add, terms, post_add), with a clear part
+        # or a LUT family (..., post_add, clear)
+        self.reqs = []
 
-    def add(self, rb: RadixBatch, j: int, lut: LookupTable, prepare=None, post_add: int = 0):
-        """prepare: (body_add, [(source batch, block, scalar), ...]); None with post_add = 0: block j as it is"""
-        if prepare is None and not post_add:
+    def add(self, rb: RadixBatch, j: int, lut, prepare=None, post_add: int = 0, clear=None):
+        """prepare: (body_add, [(source batch, block, scalar), ...]); None with post_add = 0: block j as it is.
+        clear: (_ClearRows, negate, shift, bits, scale): row r of the request also gets digit(r) * scale on the body
+        of its PBS input, digit(r) = ((negate ? -c_r : c_r) >> shift) & (2^bits - 1) of its clear operand c_r; and
+        where `lut` is a _LutFamily, row r takes its LUT number digit(r)."""
+        if clear is not None or isinstance(lut, _LutFamily):
+            body_add, terms = prepare if prepare is not None else (0, [(rb, j, 1)])
+            self.reqs.append((rb, j, lut, body_add, list(terms), post_add, clear))
+        elif prepare is None and not post_add:
             self.reqs.append((rb, j, lut))
         else:
             body_add, terms = prepare if prepare is not None else (0, [(rb, j, 1)])
@@ -158,10 +203,81 @@ class _PbsLayer:
         for rb, j, _, _, _, _ in triv:
             rb.noise[j] = NOISE_ZERO
 
+    def flush_clear(self, reqs):
+        """The layer with clear parts or LUT families: flush_fused's three calls, the first one the block layer
+        with a clear digit per row (ops.clear_block_layer).  The LUT stack of the layer holds every family whole,
+        and a request's rows take lut_base + digit(r), written to the layer's index array by the same call that
+        assembles the rows; a fixed-LUT request goes through with no clear bits (its rows take lut_base).  A layer
+        whose stack is one LUT needs no index array.  A fixed LUT whose request has a digit on the body, in a layer
+        with other LUTs, stands 2^bits times in the stack, since the one digit of an op serves body and index.
+        Trivial sources: a fixed-LUT request keeps the trivial shortcut, its op writes block j itself, clear part
+        included.  A family request goes through the batched PBS whatever its sources (the trivial PBS takes one
+        LUT for all rows) and comes out NOISE_NOMINAL: the one deviation from the reference's bookkeeping."""
+        sk, ops = self.sk, self.sk.ops
+        full = []
+        for r in reqs:
+            if len(r) == 3:
+                r = (r[0], r[1], r[2], 0, [(r[0], r[1], 1)], 0)
+            full.append(r if len(r) == 7 else r + (None,))
+        K, size, delta = full[0][0].count, sk.lwe_size, sk.p.delta
+        todo, triv = [], []
+        for req in full:
+            fixed = not isinstance(req[2], _LutFamily)
+            (triv if fixed and all(src.is_trivial_block(i) for src, i, _ in req[4]) else todo).append(req)
+        multi = len({id(r[2]) for r in todo}) > 1 or any(isinstance(r[2], _LutFamily) for r in todo)
+        copies = {}       # fixed LUTs with a digit on the body: how often they stand in a stack of several LUTs
+        for _, _, lut, _, _, _, clear in todo:
+            if multi and clear is not None and clear[3] and not isinstance(lut, _LutFamily):
+                copies[id(lut)] = max(copies.get(id(lut), 1), 1 << clear[3])
+        luts, base_of = [], {}
+        for _, _, lut, _, _, _, clear in todo:
+            if id(lut) in base_of:
+                continue
+            base_of[id(lut)] = len(luts)
+            if isinstance(lut, _LutFamily):
+                assert clear is not None and 1 << clear[3] <= len(lut.luts)
+                luts += lut.luts
+            else:
+                luts += [lut] * copies.get(id(lut), 1)
+        x = ops.rows(len(todo) * K, size) if todo else None
+        idx = ops.index_rows(len(todo) * K) if todo and multi else None
+
+        def part(clear, q=None, lut_base=0):
+            rows, negate, shift, bits, scale = clear if clear is not None else (None, 0, 0, 0, 0)
+            index = idx[q * K:(q + 1) * K] if q is not None and idx is not None else None
+            return dict(rows=rows, negate=negate, shift=shift, bits=bits, scale=scale, index=index, lut_base=lut_base)
+
+        pre = [(x[q * K:(q + 1) * K], body_add, [(ops.block(src, i), s) for src, i, s in terms],
+                part(clear, q, base_of[id(lut)])) for q, (_, _, lut, body_add, terms, _, clear) in enumerate(todo)]
+        pre += [(ops.block(rb, j), body_add, [(ops.block(src, i), s) for src, i, s in terms], part(clear))
+                for rb, j, _, body_add, terms, _, clear in triv]
+        ops.clear_block_layer(pre)
+        post = []
+        for rb, j, lut, _, _, post_add, _ in triv:
+            ops.trivial_pbs(rb, j, lut)
+            if post_add:
+                post.append((ops.block(rb, j), post_add * delta, [(ops.block(rb, j), 1)]))
+        if todo:
+            out = ops.pbs_buffer_indexed(x, luts, idx)
+            sk.pbs_count += len(todo) * K
+            sk.launches += 1
+            post += [(ops.block(rb, j), post_add * delta, [(out[q * K:(q + 1) * K], 1)])
+                     for q, (rb, j, _, _, _, post_add, _) in enumerate(todo)]
+        if post:
+            ops.block_layer(post)
+        for rb, j, lut, _, _, post_add, _ in full:
+            rb.degree[j] = lut.degree + post_add
+        for rb, j, *_ in todo:
+            rb.noise[j] = NOISE_NOMINAL
+        for rb, j, *_ in triv:
+            rb.noise[j] = NOISE_ZERO
+
     def flush(self):
         reqs, self.reqs = self.reqs, []
         if not reqs:
             return
+        if any(len(r) == 7 for r in reqs):
+            return self.flush_clear(reqs)
         if any(len(r) == 6 for r in reqs):
             return self.flush_fused(reqs)
         sk = self.sk
@@ -255,9 +371,35 @@ class _HostOps:
             acc[:, -1] += np.uint64(body_add % (1 << 64))
             dst[...] = acc
 
+    def clear_block_layer(self, ops):
+        """The block layer with a clear digit per row, the reference of the device kernel
+        (lwe_clear_block_layer_kernel): block_layer's op with a fourth member, the dict flush_clear builds.  Row r:
+            digit(r) = ((negate ? 0 - c_r : c_r) >> shift) & (2^bits - 1),   c_r = rows[r] (rows None: 0)
+            dst[r][words - 1] += digit(r) * scale,   index[r] = lut_base + digit(r)   (index None: not written)."""
+        for dst, body_add, terms, c in ops:
+            acc = np.zeros(dst.shape, dtype=np.uint64)
+            for src, scalar in terms:
+                acc += np.uint64(scalar % (1 << 64)) * src
+            digit = np.zeros(dst.shape[0], dtype=np.uint64)
+            if c["rows"] is not None:
+                v = c["rows"].on_host()
+                v = (np.uint64(0) - v) if c["negate"] else v
+                digit = (v >> np.uint64(c["shift"])) & np.uint64((1 << c["bits"]) - 1)
+            acc[:, -1] += np.uint64(body_add % (1 << 64)) + digit * np.uint64(c["scale"] % (1 << 64))
+            dst[...] = acc
+            if c["index"] is not None:
+                c["index"][...] = (np.uint64(c["lut_base"]) + digit).astype(np.uint32)
+
+    def index_rows(self, n):
+        return np.empty(n, dtype=np.uint32)
+
     def pbs_buffer(self, x, K, lut_of_request, luts):
         idx = np.repeat(np.asarray(lut_of_request, dtype=np.uint32), K)
         return self.sk.shortint.engine_ks_pbs(x, np.stack([lut.acc for lut in luts]), idx if len(luts) > 1 else None)
+
+    def pbs_buffer_indexed(self, x, luts, idx):
+        """batched KS+PBS of the rows of x, row r with LUT idx[r] of `luts` (idx None: the one LUT)"""
+        return self.sk.shortint.engine_ks_pbs(x, np.stack([lut.acc for lut in luts]), idx)
 
     def plan(self, key, luts):
         """nothing to keep on the host: every layer hands its LUTs to the engine"""
@@ -470,6 +612,54 @@ class _DeviceOps:
                     rest.append((dst, 0, tail))
             self.eng.lwe_block_layer_async(table, rows, words)
             more, first = rest, False
+
+    def clear_block_layer(self, ops):
+        """_HostOps.clear_block_layer on the device: one lwe_clear_block_layer_async call (one launch up to 25
+        ops).  The clear operands and the index array are read and written on the device, so the table holds
+        addresses only.  Terms beyond 4 go on in place through block_layer, after the call."""
+        if not ops:
+            return
+        rows, words = ops[0][0].shape
+        table, rest = [], []
+        for dst, body_add, terms, c in ops:
+            assert dst.shape == (rows, words) and dst.stride(1) == 1
+            clear = dict(negate=c["negate"], shift=c["shift"], bits=c["bits"], scale=c["scale"], lut_base=c["lut_base"])
+            if c["rows"] is not None:
+                clear["d_clear"] = c["rows"].on_device(self).data_ptr()
+            if c["index"] is not None:
+                clear["d_lut_index"] = c["index"].data_ptr()
+            table.append((dst.data_ptr(), dst.stride(0), body_add,
+                          [(src.data_ptr(), src.stride(0), scalar) for src, scalar in terms[:self.TERMS]], clear))
+            if terms[self.TERMS:]:
+                rest.append((dst, 0, [(dst, 1)] + terms[self.TERMS:]))
+        self.eng.lwe_clear_block_layer_async(table, rows, words)
+        if rest:
+            self.block_layer(rest)
+
+    def index_rows(self, n):
+        return self.torch.empty(n, dtype=self.torch.int32, device=self.device)
+
+    def _stack(self, luts):
+        """the device stack of a layer's LUTs, uploaded the first time the list is seen"""
+        key = ("stack",) + tuple(id(lut) for lut in luts)
+        hit = self._stacks.get(key)
+        if hit is None or any(a is not b for a, b in zip(hit[0], luts)):
+            hit = (list(luts), self.from_host(np.stack([lut.acc for lut in luts])))
+            self._stacks.put(key, hit)
+        return hit[1]
+
+    def pbs_buffer_indexed(self, x, luts, idx):
+        """batched KS+PBS of the rows of x, row r with LUT idx[r] of `luts` (a device int32 array the block layer
+        wrote; None: the one LUT) -> new rows"""
+        torch = self.torch
+        n = x.shape[0]
+        out = torch.empty_like(x)
+        need = self.eng.ks_pbs_scratch_bytes(n)
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self.eng.keyswitch_programmable_bootstrap_async(x, out, self._stack(luts), len(luts), n, self._scratch,
+                                                        d_lut_indexes=idx)
+        return out
 
     def pbs_buffer(self, x, K, lut_of_request, luts):
         """batched KS+PBS of the rows of x (request q: rows [qK, (q+1)K), LUT lut_of_request[q]) -> new rows"""
@@ -924,8 +1114,8 @@ class ServerKey:
     # layer is a fused _PbsLayer (flush_fused): the block arithmetic the reference does between two layers --
     # pack_block_chunk, the LWE subtraction of compare_block_assign, 4 * high + low of the sign tree, the sums
     # of eq / ne, the bivariate packing -- is the prepare op of the request that consumes it.  A BooleanBlock
-    # is a one-block RadixBatch of degree <= 1.  Out of scope: signed integers, scalar add / sub / bitwise ops /
-    # comparisons, signed div / abs and the smart_* forms.
+    # is a one-block RadixBatch of degree <= 1.  Out of scope: signed integers, signed div / abs and the smart_*
+    # forms.
     def _lut(self, key, f, bivariate: bool = False, factor: int = 0) -> LookupTable:
         """One LookupTable object per function for the life of the key: the device caches go by identity.  factor:
         a bivariate LUT whose left operand is scaled by it."""
@@ -1288,6 +1478,317 @@ class ServerKey:
         """comparator.rs:1428-1459."""
         self._require("min_parallelized", self.comparison_refusal or self.bivariate_refusal)
         return self._unchecked_min_or_max("min", self._clean(lhs), self._clean(rhs))
+
+    # ---- clear operands: scalar add / sub, bitwise ops, comparisons, min / max ----------------------------------------
+    # A clear operand is one of three things.
+    #   One Python int for the whole batch: the reference restated, its early-stop decomposers, the split into the
+    #     blocks the scalar covers and the blocks compared with zero, the trivial results for a negative or an
+    #     out-of-range scalar.  The DAG depends on the value; the digits are folded into block ops and LUT choices
+    #     on the host.
+    #   A numpy uint64 array of K values, one per row: checked against 2^T on the host, uploaded once per call.
+    #   A torch int64 tensor of K values on the engine's device, read as u64: no copy and no check (values below
+    #     2^T are the caller's promise); the form that a captured hipGraph serves with new values on every replay.
+    # The per-row forms need T = bits * blocks <= 64 and run the full-width DAG: every block takes part, as if every
+    # scalar had all its digits, and the digit of row r reaches the layer on the device (_PbsLayer.flush_clear).
+    # What a row of a per-row result equals: for scalar_add / scalar_sub the one-int form called with that row's
+    # scalar, bit for bit, always.  For the other operations bit for bit wherever the scalar's top message digit is
+    # not 0 (the reference's DAG is then the full-width one: nothing is compared with zero, no block is left out),
+    # and after decryption for smaller scalars.
+    @staticmethod
+    def _early_stop_digits(value: int, bits: int) -> list:
+        """BlockDecomposer::with_early_stop_at_zero (block_decomposition.rs): the digits up to the last non-zero one"""
+        out = []
+        while value:
+            out.append(value & ((1 << bits) - 1))
+            value >>= bits
+        return out
+
+    def _scalar_refusal(self):
+        if self.msg & (self.msg - 1):
+            return "the message modulus is not a power of two: a clear operand is decomposed into whole bits"
+        return None
+
+    def _clear(self, name: str, ct: RadixBatch, value, negative: bool = False):
+        """The clear operand of `name`: a Python int, or _ClearRows for one value per row of ct."""
+        T = self.bits * ct.num_blocks
+        per_row = "one Python int, a numpy uint64 array or a torch int64 tensor on the engine's device, of one value per row"
+        if isinstance(value, np.ndarray) or type(value).__module__.split(".")[0] == "torch":
+            host = isinstance(value, np.ndarray)
+            if str(value.dtype) not in (("uint64",) if host else ("torch.int64",)):
+                raise TypeError(f"integer {name}: the clear operand is {per_row}, got dtype {value.dtype}")
+            if tuple(value.shape) != (ct.count,):
+                raise ValueError(f"integer {name}: {ct.count} rows against clear operands of shape {tuple(value.shape)}")
+            self._require(name, None if T <= 64 else
+                          f"one clear operand per row is one u64, and the ciphertexts hold {T} bits")
+            if host:
+                if T < 64 and (value >> np.uint64(T)).any():
+                    raise ValueError(f"integer {name}: a clear operand per row must be below 2^{T}, the ciphertexts' range")
+                return _ClearRows(host=np.ascontiguousarray(value))
+            if isinstance(self.ops, _DeviceOps) and (value.device != self.ops.device or not value.is_contiguous()):
+                raise ValueError(f"integer {name}: the clear operands must be contiguous on {self.ops.device}, "
+                                 f"got {value.device}")
+            return _ClearRows(dev=value)
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise TypeError(f"integer {name}: the clear operand is {per_row}, got {type(value).__name__}")
+        if value < 0 and not negative:
+            raise ValueError(f"integer {name}: the clear operand must not be negative, got {value}")
+        return int(value)
+
+    def _family(self, key, functions) -> _LutFamily:
+        """the family of the LUTs _lut(key + (s,), functions[s]), cached like them"""
+        t = self._luts.get(("family",) + key)
+        if t is None:
+            t = self._luts[("family",) + key] = _LutFamily([self._lut(key + (s,), f) for s, f in enumerate(functions)])
+        return t
+
+    # -- scalar add / sub -----------------------------------------------------------------------------------------------
+    def _unchecked_scalar_add_assign(self, ct: RadixBatch, clear, negate: bool):
+        """unchecked_scalar_add_assign (radix/scalar_add.rs:53-65) and unchecked_scalar_sub_assign
+        (radix/scalar_sub.rs:109-122): block j gets the digit of the scalar, or of its negation
+        (create_negated_block_decomposer, scalar_sub.rs:68-107: the two's complement, padded with ones), times delta
+        on its body (shortint unchecked_scalar_add_assign), and its degree grows by the digit.  No PBS, one
+        block-layer call.  One value per row: one clear block-layer call over every block, and every degree grows
+        by msg - 1, the largest digit, whatever the values are (numpy arrays included: the DAG that follows must
+        not depend on them)."""
+        nb, bits, delta = ct.num_blocks, self.bits, self.p.delta
+        if isinstance(clear, _ClearRows):
+            self.ops.clear_block_layer([
+                (self.ops.block(ct, j), 0, [(self.ops.block(ct, j), 1)],
+                 dict(rows=clear, negate=int(negate), shift=j * bits, bits=bits, scale=delta, index=None, lut_base=0))
+                for j in range(nb)])
+            ct.degree = [d + self.msg - 1 for d in ct.degree]
+            return
+        if negate:
+            digits = [((-clear) >> (j * bits)) & (self.msg - 1) for j in range(nb)] if clear else []
+        else:
+            digits = self._early_stop_digits(clear, bits)[:nb]
+        self.ops.block_layer([(self.ops.block(ct, j), d * delta, [(self.ops.block(ct, j), 1)])
+                              for j, d in enumerate(digits) if d])
+        for j, d in enumerate(digits):
+            ct.degree[j] += d
+
+    def _scalar_add(self, op: str, ct: RadixBatch, scalar, unchecked: bool, assign: bool):
+        """{unchecked_,}scalar_{add,sub}[_assign]: the default forms (radix_parallel/scalar_add.rs:249-265,
+        scalar_sub.rs:99-115) propagate a dirty operand first and the single carries afterwards; the assign forms
+        take a resident operand."""
+        name = (f"unchecked_scalar_{op}" + ("_assign" if assign else "") if unchecked else
+                f"scalar_{op}" + ("_assign" if assign else "") + "_parallelized")
+        clear = self._clear(name, ct, scalar)
+        self._require(name, self._scalar_refusal() or (None if unchecked else self.propagation_refusal))
+        res = ct if assign else self._resident(ct).clone()
+        if not unchecked and not res.block_carries_are_empty(self.msg):
+            self.full_propagate(res)
+        self._unchecked_scalar_add_assign(res, clear, op == "sub")
+        if not unchecked:
+            self._propagate_single_carry_low_latency(res)
+        return None if assign else res
+
+    # -- scalar bitwise ops ---------------------------------------------------------------------------------------------
+    def _scalar_bitop(self, op: str, lhs: RadixBatch, scalar, unchecked: bool, assign: bool):
+        """{unchecked_,}scalar_bit{and,or,xor}[_assign]_parallelized (radix_parallel/scalar_bitwise_op.rs:17-45,
+        127-136, 148-170, 273-295) over shortint unchecked_scalar_bit*_assign (shortint scalar_bitwise_op.rs:50, 110,
+        169: the LUT x -> (x % msg op s) % msg): one PBS per block the scalar's digits cover; beyond its last digit
+        bitand leaves trivial zeros and the other two leave the blocks as they are.  One value per row: every block,
+        with the family of the msg LUTs of a digit; its degree is the largest of the family's, msg - 1."""
+        name = ("unchecked_" if unchecked else "") + f"scalar_{op}" + ("_assign" if assign else "") + "_parallelized"
+        clear = self._clear(name, lhs, scalar)
+        self._require(name, self._scalar_refusal())
+        res = lhs if assign else self._resident(lhs).clone()
+        if not unchecked and not res.block_carries_are_empty(self.msg):
+            self.full_propagate(res)
+        f, m, nb, bits = self._BITOPS[op][0], self.msg, res.num_blocks, self.bits
+        functions = [lambda x, s=s: f(x % m, s) % m for s in range(m)]
+        layer = _PbsLayer(self)
+        if isinstance(clear, _ClearRows):
+            family = self._family((f"scalar_{op}",), functions)
+            for j in range(nb):
+                layer.add(res, j, family, clear=(clear, 0, j * bits, bits, 0))
+            layer.flush()
+        else:
+            digits = self._early_stop_digits(clear, bits)[:nb]
+            for j, s in enumerate(digits):
+                layer.add(res, j, self._lut((f"scalar_{op}", s), functions[s]))
+            layer.flush()
+            if op == "bitand":
+                for j in range(len(digits), nb):
+                    self._set_trivial(res, j, 0)
+        return None if assign else res
+
+    # -- scalar eq / ne ---------------------------------------------------------------------------------------------------
+    def _trivial_block(self, count: int, value: int) -> RadixBatch:
+        """create_trivial / create_trivial_boolean_block: one trivial block holding `value` in every row"""
+        rb = self.create_trivial_zero(count, 1)
+        if value:
+            self._set_trivial(rb, 0, value)
+        return rb
+
+    def _one_block(self, rb: RadixBatch, j: int) -> RadixBatch:
+        """block j of rb as a batch of its own"""
+        if rb.num_blocks == 1:
+            return rb
+        out = self._new(rb.count, 1)
+        self.ops.block_layer([(self.ops.block(out, 0), 0, [(self.ops.block(rb, j), 1)])])
+        out.degree, out.noise = [rb.degree[j]], [rb.noise[j]]
+        return out
+
+    def _packed(self, lhs: RadixBatch, chunk: list) -> list:
+        """pack_block_chunk (scalar_comparison.rs:104-138) as prepare terms: msg * high + low, or the one block"""
+        return [(lhs, chunk[1], self.msg), (lhs, chunk[0], 1)] if len(chunk) == 2 else [(lhs, chunk[0], 1)]
+
+    def _unchecked_scalar_equality(self, op: str, lhs: RadixBatch, clear) -> RadixBatch:
+        """unchecked_scalar_{eq,ne}_parallelized (scalar_comparison.rs:366-558), unsigned: a negative scalar and one
+        with a non-zero packed digit beyond the ciphertext give a trivial answer; pairs of blocks the scalar's packed
+        digits cover are packed and compared with the digit by the LUT x -> x == s (create_scalar_comparison_luts,
+        :312-336), the blocks above are compared with zero in the same pass (compare_blocks_with_zero), and the
+        0 / 1 blocks are reduced (are_all_ / is_at_least_one_comparisons_block_true).  A packed digit is
+        2 * log2(msg) bits, the reference's total_modulus.ilog2() where carry == msg.  One value per row: every
+        pair, with the family of the msg^2 LUTs of a packed digit; an odd last block takes the digits below msg of
+        the same family."""
+        eq, m, nb, K, pbits = op == "eq", self.msg, lhs.num_blocks, lhs.count, 2 * self.bits
+        assert nb > 0 and lhs.block_carries_are_empty(m)
+        compare = (lambda x, s: int(x == s)) if eq else (lambda x, s: int(x != s))
+        functions = [lambda x, s=s: compare(x, s) for s in range(m * m)]
+        chunks = [list(range(j, min(j + 2, nb))) for j in range(0, nb, 2)]
+        layer = _PbsLayer(self)
+        if isinstance(clear, _ClearRows):
+            family = self._family((f"scalar_{op}",), functions)
+            out = self._new(K, len(chunks))
+            for c, chunk in enumerate(chunks):
+                layer.add(out, c, family, prepare=(0, self._packed(lhs, chunk)),
+                          clear=(clear, 0, c * pbits, pbits if len(chunk) == 2 else self.bits, 0))
+            layer.flush()
+            blocks = [(out, c) for c in range(len(chunks))]
+        else:
+            if clear < 0:
+                return self._trivial_block(K, int(not eq))
+            digits = self._early_stop_digits(clear, pbits)
+            if any(digits[len(chunks):]):                     # is_scalar_obviously_bigger
+                return self._trivial_block(K, int(not eq))
+            digits = digits[:len(chunks)]
+            split = min(nb, 2 * len(digits))
+
+            def covered():
+                if not digits:
+                    return []
+                out = self._new(K, len(digits))
+                for c, s in enumerate(digits):
+                    layer.add(out, c, self._lut((f"scalar_{op}", s), functions[s]), prepare=(0, self._packed(lhs, chunks[c])))
+                yield
+                return [(out, c) for c in range(len(digits))]
+
+            low, high = self._join(layer, covered(), self._compare_blocks_with_zero_steps(
+                layer, [(lhs, j) for j in range(split, nb)], eq))
+            blocks = low + high
+        (res,) = self._join(layer, self._comparisons_block_true_steps(layer, K, blocks, eq))
+        return self._one_block(*res)
+
+    # -- scalar order -----------------------------------------------------------------------------------------------------
+    def _reduce_signs_steps(self, layer: _PbsLayer, count: int, blocks: list):
+        """reduce_signs_parallelized (comparator.rs:257-280) as a branch of _join: pairs 4 * high + low through
+        comparison_reduction_lut until one sign is left"""
+        table = [IS_INFERIOR] * 5 + [IS_EQUAL] + [IS_SUPERIOR] * 5
+        reduction = self._lut(("sign_reduction",), lambda x: table[x] if x < len(table) else 0)
+        while len(blocks) != 1:
+            out = self._new(count, len(blocks) // 2)
+            for c in range(len(blocks) // 2):
+                (low, lj), (high, hj) = blocks[2 * c], blocks[2 * c + 1]
+                layer.add(out, c, reduction, prepare=(0, [(high, hj, 4), (low, lj, 1)]))
+            yield
+            blocks = [(out, c) for c in range(len(blocks) // 2)] + (blocks[-1:] if len(blocks) % 2 else [])
+        return blocks[0]
+
+    def _unchecked_scalar_compare(self, lhs: RadixBatch, clear):
+        """unsigned_unchecked_scalar_compare_blocks_parallelized (comparator.rs:677-783): the sign (batch, block) of
+        lhs against the scalar.  The blocks the scalar's digits cover are packed in pairs, the packed digit times
+        delta is subtracted on the body, sign_lut, + 1 (scalar_compare_block_assign, :226-238), and the signs are
+        reduced; the blocks above are compared with zero, reduced, and mapped to IS_EQUAL / IS_SUPERIOR; both
+        branches share their passes (rayon::join), and one more reduction joins the two signs.  One value per row:
+        every pair, the packed digit of row r times -delta from the clear block layer."""
+        m, nb, K, bits, delta = self.msg, lhs.num_blocks, lhs.count, self.bits, self.p.delta
+        assert nb > 0 and lhs.block_carries_are_empty(m)
+        sign_lut = self._lut(("sign",), lambda x: int(x != 0))
+        layer = _PbsLayer(self)
+        if isinstance(clear, _ClearRows):
+            chunks = [list(range(j, min(j + 2, nb))) for j in range(0, nb, 2)]
+            signs = self._new(K, len(chunks))
+            for c, chunk in enumerate(chunks):
+                layer.add(signs, c, sign_lut, prepare=(0, self._packed(lhs, chunk)), post_add=1,
+                          clear=(clear, 0, c * 2 * bits, len(chunk) * bits, -delta))
+            layer.flush()
+            (sign,) = self._join(layer, self._reduce_signs_steps(layer, K, [(signs, c) for c in range(len(chunks))]))
+            return sign
+        if clear < 0:
+            return self._trivial_block(K, IS_SUPERIOR), 0
+        digits = self._early_stop_digits(clear, bits)
+        if any(digits[nb:]):                                  # is_scalar_obviously_bigger
+            return self._trivial_block(K, IS_INFERIOR), 0
+        digits = digits[:nb]
+
+        def covered():
+            chunks = [list(range(j, min(j + 2, len(digits)))) for j in range(0, len(digits), 2)]
+            signs = self._new(K, len(chunks))
+            for c, chunk in enumerate(chunks):
+                packed = sum(digits[j] * m ** i for i, j in enumerate(chunk))
+                layer.add(signs, c, sign_lut, prepare=(-packed * delta, self._packed(lhs, chunk)), post_add=1)
+            yield
+            return (yield from self._reduce_signs_steps(layer, K, [(signs, c) for c in range(len(chunks))]))
+
+        def above():
+            zero = yield from self._compare_blocks_with_zero_steps(layer, [(lhs, j) for j in range(len(digits), nb)], True)
+            rb, j = yield from self._comparisons_block_true_steps(layer, K, zero, True)
+            out = self._new(K, 1)
+            layer.add(out, 0, self._lut(("sign_of_upper_zero",), lambda x: IS_EQUAL if x == 1 else IS_SUPERIOR),
+                      prepare=(0, [(rb, j, 1)]))
+            yield
+            return out, 0
+
+        signs = self._join(layer, *([covered()] if digits else []), *([above()] if len(digits) < nb else []))
+        if len(signs) == 1:
+            return signs[0]
+        (low, lj), (high, hj) = signs                         # reduce_two_sign_blocks_assign(msb_sign, lsb_sign)
+        (sign,) = self._join(layer, self._reduce_signs_steps(layer, K, [(low, lj), (high, hj)]))
+        return sign
+
+    def _trivial_radix(self, count: int, nb: int, clear) -> RadixBatch:
+        """create_trivial_radix (radix/mod.rs): the digits of the scalar modulo 2^T as trivial blocks, of the
+        digit's degree.  One value per row: one clear block-layer call of term-less ops (a zero mask, the digit
+        times delta on the body), degree msg - 1."""
+        if isinstance(clear, _ClearRows):
+            rb = self._new(count, nb)
+            self.ops.clear_block_layer([
+                (self.ops.block(rb, j), 0, [], dict(rows=clear, negate=0, shift=j * self.bits, bits=self.bits,
+                                                    scale=self.p.delta, index=None, lut_base=0)) for j in range(nb)])
+            rb.degree = [self.msg - 1] * nb
+            return rb
+        rb = self.create_trivial_zero(count, nb)
+        for j in range(nb):
+            digit = (clear >> (j * self.bits)) & (self.msg - 1)
+            if digit:
+                self._set_trivial(rb, j, digit)
+        return rb
+
+    def _scalar_comparison(self, op: str, lhs: RadixBatch, scalar, unchecked: bool) -> RadixBatch:
+        """{unchecked_,}scalar_{eq,ne,gt,ge,lt,le,max,min}_parallelized (scalar_comparison.rs:366-680,
+        comparator.rs:877-912, 1468-1535, 1618-1710): the default forms work on a propagated clone of a dirty
+        operand.  eq / ne need carry >= msg, as the reference asserts (:399); the order comparisons pack as well."""
+        name = ("unchecked_" if unchecked else "") + f"scalar_{op}_parallelized"
+        clear = self._clear(name, lhs, scalar, negative=True)
+        refusal = self.bivariate_refusal if op in ("eq", "ne") else (self.comparison_refusal or self.bivariate_refusal)
+        self._require(name, self._scalar_refusal() or refusal)
+        lhs = self._resident(lhs) if unchecked else self._clean(lhs)
+        if op in ("eq", "ne"):
+            return self._unchecked_scalar_equality(op, lhs, clear)
+        sign, sj = self._unchecked_scalar_compare(lhs, clear)
+        if op in self._ORDER:                                 # map_sign_result (comparator.rs:957-971)
+            res = self._new(lhs.count, 1)
+            layer = _PbsLayer(self)
+            layer.add(res, 0, self._lut(("sign_is", op), lambda x, f=self._ORDER[op]: int(f(x))),
+                      prepare=(0, [(sign, sj, 1)]))
+            layer.flush()
+            return res
+        keep = IS_SUPERIOR if op == "max" else IS_INFERIOR    # unchecked_scalar_min_or_max_parallelized
+        rhs = self._trivial_radix(lhs.count, lhs.num_blocks, clear)
+        return self._programmable_if_then_else(sign, sj, lhs, rhs, op, lambda x: x == keep)
 
     # ---- shifts and rotations by a clear amount, by an encrypted amount, scalar_mul -------------------------------
     # Every PBS layer is a fused _PbsLayer again.  A block rotation is never a data movement: it is the source block
@@ -1851,8 +2352,39 @@ def _add_shift_methods():
                     setattr(ServerKey, name, f)
 
 
+def _add_scalar_methods():
+    """the public names of the clear-operand forms, as the reference has them: unchecked_scalar_{add,sub}[_assign]
+    and scalar_{add,sub}[_assign]_parallelized; the four forms of scalar_bit{and,or,xor}; unchecked_ and default
+    scalar_{eq,ne,gt,ge,lt,le,max,min}_parallelized"""
+    def named(name, f):
+        f.__name__ = f.__qualname__ = name
+        setattr(ServerKey, name, f)
+
+    def add(op, unchecked, assign):
+        return lambda self, ct, scalar: self._scalar_add(op, ct, scalar, unchecked, assign)
+
+    def bitop(op, unchecked, assign):
+        return lambda self, ct, scalar: self._scalar_bitop(op, ct, scalar, unchecked, assign)
+
+    def comparison(op, unchecked):
+        return lambda self, ct, scalar: self._scalar_comparison(op, ct, scalar, unchecked)
+
+    for assign in (False, True):
+        tail = "_assign" if assign else ""
+        for op in ("add", "sub"):
+            named(f"unchecked_scalar_{op}{tail}", add(op, True, assign))
+            named(f"scalar_{op}{tail}_parallelized", add(op, False, assign))
+        for op in ServerKey._BITOPS:
+            named(f"unchecked_scalar_{op}{tail}_parallelized", bitop(op, True, assign))
+            named(f"scalar_{op}{tail}_parallelized", bitop(op, False, assign))
+    for op in ("eq", "ne", "max", "min") + tuple(ServerKey._ORDER):
+        named(f"unchecked_scalar_{op}_parallelized", comparison(op, True))
+        named(f"scalar_{op}_parallelized", comparison(op, False))
+
+
 _add_shift_methods()
 _add_div_methods()
+_add_scalar_methods()
 
 
 # ---- integer WoP-PBS (integer/wopbs/mod.rs) ----------------------------------------------------------
