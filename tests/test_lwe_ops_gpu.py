@@ -1,6 +1,6 @@
 """The integer layer's device glue (csrc/lwe_ops.hip: lwe_scalar_mul_add_kernel, trivial_pbs_kernel)
-against numpy u64 arithmetic, on one 2_2 engine with no keys.  Elsewhere these kernels run only inside
-the 32-bit multiplication of test_integer_gpu.py, at one stride and one LUT.
+against numpy u64 arithmetic, on engines with no keys: one of 2_2, and for the trivial PBS one of each of 1_1,
+2_2, 3_3 and 4_4.  Elsewhere these kernels run only inside the radix integer DAGs, at their strides and LUTs.
 """
 import numpy as np
 import pytest
@@ -74,12 +74,27 @@ def test_lwe_scalar_mul_add_refuses_a_stride_below_the_row(eng):
         eng.lwe_scalar_mul_add_async(d_y.data_ptr(), d_y.data_ptr(), 3, 3, WORDS, WORDS, WORDS - 1)
 
 
-def test_trivial_pbs(orc, eng, params_2_2):
+# (set, words of a row): the big LWE size of each set, and the 743 words of the 2_2 instance this test began with.
+# delta, modulus_sup, box, k: 2^61, 4, 128, 3 | 2^59, 16, 128, 1 | 2^57, 64, 128, 1 | 2^55, 256, 128, 1
+TRIVIAL_PBS = [("2_2", WORDS), ("1_1", 3 * 512 + 1), ("2_2", 2048 + 1), ("3_3", 8192 + 1), ("4_4", 32768 + 1)]
+
+
+@pytest.mark.parametrize("name,words", TRIVIAL_PBS, ids=[f"{n}-{w}" for n, w in TRIVIAL_PBS])
+def test_trivial_pbs(orc, name, words):
     """bodies v delta and v delta + delta - 1 for every v in [0, 2 msup), and 2^64 - 1 (v = 2 msup - 1),
-    cycled over 257 rows (a second workgroup) of stride 750 > 743: the body becomes the LUT's box value
-    of v mod msup, negated from the padding bit on; the (zero) masks and the words between the rows stay."""
-    p = params_2_2
+    cycled over 257 rows at least (a second workgroup) of stride words + 7: the body becomes the LUT's box value
+    of v mod msup, negated from the padding bit on; the (zero) masks and the words between the rows stay.
+    One engine per set, no keys: the kernel takes delta, modulus_sup, box and the body's offset k N in the LUT
+    from the engine's parameters."""
+    from tfhe_mi355 import Engine
+    from tfhe_mi355.parameters import SHORTINT_ALL
+
+    m, c = name.split("_")
+    p = SHORTINT_ALL[f"PARAM_MESSAGE_{m}_CARRY_{c}_KS_PBS"]
+    eng = Engine(p, 0)
+    WORDS = words  # noqa: N806  (the body below is the 2_2 test's, word for word)
     N, k = p.polynomial_size, p.glwe_dimension
+    assert words == 743 or words == k * N + 1
     msup, delta = p.message_modulus * p.carry_modulus, p.delta
     box = N // msup
     f = lambda m: (5 * m + 3) % msup  # noqa: E731  (a bijection: every box differs)
@@ -89,7 +104,7 @@ def test_trivial_pbs(orc, eng, params_2_2):
     vs = list(range(2 * msup))
     bodies = [v * delta for v in vs] + [v * delta + delta - 1 for v in vs] + [2 ** 64 - 1]
     values = vs + vs + [2 * msup - 1]
-    rows, stride = 257, 750
+    rows, stride = max(257, len(bodies)), WORDS + 7       # 4_4 has 1025 bodies: every one gets a row
     pick = np.arange(rows) % len(bodies)
     buf = np.zeros((rows, stride), dtype=U64)
     buf[:, WORDS:] = U64(SENTINEL)

@@ -2095,6 +2095,11 @@ class ServerKey:
                 assert lo.degree[lj] + 1 <= m and hi.degree[hj] * m + lo.degree[lj] < total
                 layer.add(*step[b], self.lut_prefix, prepare=(0, [(hi, hj, m), (lo, lj, 1)]))
             yield
+            for rb, j in step[space:]:
+                # the prefix of borrow states is a borrow state, though the LUT that made it has degree msg - 1: with
+                # carry < msg that degree would not pack in the next step, the states do (the reference packs them
+                # unchecked, bivariate_pbs.rs:167-182)
+                rb.degree[j] = BORROW_PROPAGATED
             states, space = step, space * 2
         res = self._new(count, nb)
         for j in range(nb):          # block j takes the output borrow of block j - 1, block 0 a trivial zero: no term
