@@ -1,5 +1,5 @@
 """Device time of one async PBS launch at 2_2 for a range of batch sizes (HIP events on the launch
-stream), to place the latency/throughput kernel switch (TFHE_MI355_LATENCY_MAX, capi.cpp).
+stream), to place the latency/throughput kernel switch (TFHE_MI355_LATENCY_MAX, capi_pbs.cpp).
 Run it twice, with TFHE_MI355_LATENCY_MAX=0 (throughput kernel only) and =4096 (latency kernel
 for every count), and compare.  Prints one JSON line."""
 import json

@@ -62,7 +62,7 @@ def covered_entry_points():
 
 # ---- small helpers --------------------------------------------------------------------------------------
 def _cus():
-    """Compute units of device 0: the kernel-form thresholds of capi.cpp scale with it."""
+    """Compute units of device 0: the kernel-form thresholds of capi_pbs.cpp scale with it."""
     import torch
 
     return torch.cuda.get_device_properties(0).multi_processor_count
@@ -310,7 +310,7 @@ def _pbs_case(form, count, kernels, scratch_cts=None, seed=1):
 
 
 def _lat(cus):
-    return 3 * cus  # capi.cpp latency_max, classic
+    return 3 * cus  # capi_pbs.cpp latency_max, classic
 
 
 # classic N <= 2048: programmable_bootstrap_async and blind_rotate_async
@@ -336,11 +336,11 @@ case("multibit-8192-g3-pbs-3-scratch2", "mb8192", ["programmable_bootstrap_async
 
 
 def _quad(cus):
-    return cus // 2   # capi.cpp quad_max at N = 4096
+    return cus // 2   # capi_pbs.cpp quad_max at N = 4096
 
 
 def _onchip(cus):
-    return cus * 5 // 8  # capi.cpp onchip_min at N = 4096
+    return cus * 5 // 8  # capi_pbs.cpp onchip_min at N = 4096
 
 
 # classic N >= 4096: scratch = pbs_scratch_bytes(1) x m

@@ -62,7 +62,7 @@ def test_flop_models():
 
 
 def test_split_chunk_matches_the_engine_rule():
-    """bench.split_chunk mirrors capi.cpp large_chunk: 200 MiB of (acc + spectra) per pass, a
+    """bench.split_chunk mirrors capi_pbs.cpp large_chunk: 200 MiB of (acc + spectra) per pass, a
     multiple of 64 in [64, 1024], 128 at N = 32768, 1024 for multi-bit."""
     from tfhe_mi355.parameters import ALL
 

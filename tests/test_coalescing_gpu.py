@@ -2,7 +2,7 @@
 threads at once (shortint keyswitch_programmable_bootstrap_assign, shortint/server_key/mod.rs:
 783-857, called from rayon workers per block, integer/server_key/radix_parallel/mul.rs:347-407).
 
-Small host-pointer calls on one context are coalesced into batches (capi.cpp "request
+Small host-pointer calls on one context are coalesced into batches (capi_pipeline.cpp "request
 coalescing"): every caller must still get exactly its own rows -- bit-exact against the oracle's
 keyswitch + PBS of the same ciphertext with the same LUT -- whatever the batch it landed in, with
 different LUTs per caller (deduplicated by buffer), per-row LUT indexes and different ops
@@ -74,7 +74,7 @@ def test_16_threads_x_64_single_ciphertext_ks_pbs_bit_exact(orc, keys_2_2, eng):
 
 def test_lone_caller_runs_directly_and_exactly(orc, keys_2_2):
     """One blocking caller at a time on a fresh context: every call runs at once on the calling
-    thread (capi.cpp coalesced_call: a batch of its own, never counted in flight), with the same
+    thread (capi_pipeline.cpp coalesced_call: a batch of its own, never counted in flight), with the same
     rows as the oracle; KS+PBS with two LUTs and a per-row index through the same path."""
     from tfhe_mi355 import Engine
 

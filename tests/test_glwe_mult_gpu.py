@@ -1,5 +1,5 @@
 """The GLWE product with relinearisation on the GPU (csrc/glwe_mult.hip and its entry points in
-csrc/capi.cpp), bit-exact (np.array_equal) against the CPU reference of tests/glwe_mult_reference.py,
+csrc/capi_gadget.cpp), bit-exact (np.array_equal) against the CPU reference of tests/glwe_mult_reference.py,
 which is built from the oracle (tests/test_glwe_mult.py checks that reference).
 
 Engine.glwe_mult runs on arbitrary words (exactness needs no valid ciphertext or key).  Shapes (k, N):

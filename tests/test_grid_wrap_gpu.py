@@ -137,7 +137,7 @@ def test_block_layer_grid_constants_are_the_source():
 
 # ---- b. ticket trips under the hook -------------------------------------------------------------------------------
 def _rows(shape):
-    """19 rows; (2048, 1, 1): 3 CUs + 5, the first count past the latency kernel's (capi.cpp latency_max:
+    """19 rows; (2048, 1, 1): 3 CUs + 5, the first count past the latency kernel's (capi_pbs.cpp latency_max:
     TFHE_MI355_LATENCY_MAX is read once per process, so the row count selects the kernel)"""
     return 3 * PS._cus() + 5 if shape == (2048, 1, 1) else 19
 

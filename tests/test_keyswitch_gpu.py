@@ -3,7 +3,7 @@ small-base arm of csrc/pfpks.hip) bit-exact against the oracle, and at the small
 numpy reference of test_keyswitch_reference.py, on that file's edge rows.  Keys are random u64 words
 (exactness needs no valid key); engines come from params_2_2.with_(...) with no bootstrap key.
 
-In process (the int8-MFMA arm, asserted through the scratch queries: capi.cpp returns 0 bytes exactly
+In process (the int8-MFMA arm, asserted through the scratch queries: capi_pbs.cpp returns 0 bytes exactly
 when the scalar arm is chosen): the column-tile edges out_dim + 1 = 63, 64, 65, 130 at counts 1, 6
 and 67; every decomposition of parameters.py and (7, 9), (1, 16), (3, 17); the input shape (N, k) =
 (256, 5); the unsplit launch (gridDim.z == 1) reached by construction with 16 x 8 = 128 tiles; the

@@ -77,7 +77,7 @@ def _large_keys(orc, p, seed):
 
 
 def _cus():
-    """Compute units of device 0: the CMUX form thresholds of capi.cpp scale with it."""
+    """Compute units of device 0: the CMUX form thresholds of capi_pbs.cpp scale with it."""
     import torch
 
     return torch.cuda.get_device_properties(0).multi_processor_count
@@ -244,7 +244,7 @@ def test_large_shape_crafted_digits(orc, case):
 def test_one_level_three_cmux_forms(orc, N, B):
     """N = 4096 / 8192, L = 1 at base 2^30 (the last 32-bit digit) and 2^31 (the 64-bit one-level arm:
     quad_cmux_kernel / onchip_cmux_kernel <N, false, 1> and decompose64<1> in the top stage): the same
-    rows through the on-chip CMUX (one call above capi.cpp onchip_min), the quad / duo CMUX (calls of
+    rows through the on-chip CMUX (one call above capi_pbs.cpp onchip_min), the quad / duo CMUX (calls of
     1, 7 and CUs/R - 12 rows, at most quad_max) and the split CMUX (the rest, between the two), each
     kernel checked by the engine's kernel timer; every row identical, 9 sampled rows equal to the
     oracle, the crafted triple (rows 0 .. 2, crafted LUT) among them."""
@@ -255,7 +255,7 @@ def test_one_level_three_cmux_forms(orc, N, B):
     try:
         cus = _cus()
         R = N // 2048
-        Q, O = cus // R, cus * (5 if R == 2 else 3) // 8  # capi.cpp quad_max, onchip_min
+        Q, O = cus // R, cus * (5 if R == 2 else 3) // 8  # capi_pbs.cpp quad_max, onchip_min
         C = max(O + 35, Q - 4 + (Q + O) // 2)  # the last call (Q - 4 .. C) lands between Q and O
         rng = np.random.default_rng(N + B)
         cts = rng.integers(0, 2 ** 64, (C, n + 1), dtype=U64)

@@ -9,7 +9,7 @@ and that every value is the same.  Queries allocate nothing, so the full-size pa
 each and no more.
 
   keyless contexts (2_2, mb3, 3_3 at N = 8192, 4_4 at N = 32768, mb3_3g3): the PBS, KS, KS -> PBS and
-    PBS -> KS queries at counts 0, 1, 5, 300 and 1025 (past the multi-bit large_chunk of 1024, capi.cpp);
+    PBS -> KS queries at counts 0, 1, 5, 300 and 1025 (past the multi-bit large_chunk of 1024, capi_pbs.cpp);
   the small keyed engines of test_async_guards_gpu.py (ks512, mult1024, ggsw, wop512, the two Boolean
     shapes, the two 128-bit ones): every query of the header at counts 0, 1, 5 and 300, both pbs_order
     values for gates and mux, two (nbits, cbs_level, nout, npoly) tuples for the vertical-packing queries.

@@ -51,7 +51,7 @@ def _device_to_host(ptr, nbytes):
 
 
 def _cus():
-    """Compute units of device 0: the CMUX form thresholds of capi.cpp scale with it."""
+    """Compute units of device 0: the CMUX form thresholds of capi_pbs.cpp scale with it."""
     import torch
 
     return torch.cuda.get_device_properties(0).multi_processor_count
@@ -168,7 +168,7 @@ def test_split_pbs_chunks_ragged(orc):
                                   "PARAM_MESSAGE_2_CARRY_3_KS_PBS"])   # N = 4096, L = 1
 def test_onchip_and_split_cmux_agree(orc, name):
     """N = 8192 and 4096, L = 2 and 1: one call of C ciphertexts runs the on-chip CMUX (onchip_cmux_kernel;
-    capi.cpp onchip_min: >= 96 rows at N = 8192, >= 160 at N = 4096 on 256 CUs; at N = 4096 two
+    capi_pbs.cpp onchip_min: >= 96 rows at N = 8192, >= 160 at N = 4096 on 256 CUs; at N = 4096 two
     ciphertexts per workgroup, the odd count leaving a padding slot), the same ciphertexts in two calls
     below the threshold the split CMUX (digits-fed at L = 2, three launches at L = 1) or, at most
     CUs / R rows, the quad / duo CMUX; every row
@@ -180,10 +180,10 @@ def test_onchip_and_split_cmux_agree(orc, name):
     lwe_sk, glwe_sk, bsk, fbsk = _keys(orc, p, 77)
     eng = _engine(p, bsk)
     cus = _cus()
-    on_min = cus * 3 // 8 if p.polynomial_size == 8192 else cus * 5 // 8  # capi.cpp onchip_min
+    on_min = cus * 3 // 8 if p.polynomial_size == 8192 else cus * 5 // 8  # capi_pbs.cpp onchip_min
     C = on_min + 35
     h = C // 2
-    quad = h <= cus // (p.polynomial_size // 2048)  # capi.cpp quad_max (quad / duo, L = 1 and 2)
+    quad = h <= cus // (p.polynomial_size // 2048)  # capi_pbs.cpp quad_max (quad / duo, L = 1 and 2)
     msgs = np.random.default_rng(5).integers(0, space, C)
     cts = orc.lwe_encrypt(78, lwe_sk, msgs.astype(np.uint64) * np.uint64(p.delta), p.lwe_modular_std_dev)
     cts[0, :-1] = 0                                   # every a~ = 0
@@ -213,7 +213,7 @@ def test_onchip_and_split_cmux_agree(orc, name):
 def test_quad_onchip_and_split_cmux_agree(orc, name):
     """N = 8192 and 4096, L = 2 and 1: the same ciphertexts through the three CMUX forms -- one call above
     the on-chip threshold (on-chip CMUX, one ciphertext per CU), calls of 1, 7 and CUs/R - 12 (quad /
-    duo CMUX: R = N / 2048 workgroups per ciphertext exchanging their sub-blocks every CMUX; capi.cpp
+    duo CMUX: R = N / 2048 workgroups per ciphertext exchanging their sub-blocks every CMUX; capi_pbs.cpp
     quad_max = CUs / R) and one call of the rest (split CMUX, between the quad and the on-chip ranges),
     the kernel of each call checked by the engine's kernel timer -- every row identical, a sample
     bit-exact against the oracle, edge masks and per-ciphertext LUTs included."""
@@ -225,7 +225,7 @@ def test_quad_onchip_and_split_cmux_agree(orc, name):
     eng = _engine(p, bsk)
     cus = _cus()
     R = p.polynomial_size // 2048
-    Q, O = cus // R, cus * (5 if R == 2 else 3) // 8  # capi.cpp quad_max, onchip_min
+    Q, O = cus // R, cus * (5 if R == 2 else 3) // 8  # capi_pbs.cpp quad_max, onchip_min
     C = max(O + 35, Q - 4 + (Q + O) // 2)  # the last call (Q - 4 .. C) lands between Q and O
     msgs = np.random.default_rng(8).integers(0, space, C)
     cts = orc.lwe_encrypt(80, lwe_sk, msgs.astype(np.uint64) * np.uint64(p.delta), p.lwe_modular_std_dev)

@@ -1,5 +1,5 @@
 """The bootstrapped half of WoP-PBS on the GPU (csrc/pfpks.hip, the WoP glue of csrc/lwe_ops.hip and
-the launch structure of csrc/capi.cpp), bit-exact (np.array_equal) against the CPU reference of
+the launch structure of csrc/capi_wopbs.cpp), bit-exact (np.array_equal) against the CPU reference of
 tests/wopbs_reference.py, which is built from the oracle (tests/test_wopbs.py checks that reference).
 
 pfpks shapes (N, k, base_log, level), random u64 keys (exactness needs no valid key): (2048, 1, 15, 2)

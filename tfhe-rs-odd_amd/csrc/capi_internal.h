@@ -1,9 +1,11 @@
 // capi_internal.h -- what the capi*.cpp files share: the host-side runtime behind include/tfhe_mi355.h is
-// split by subsystem (capi.cpp: contexts, keys, kernel-form policy, the u64 launchers and entry points with
-// the host-pointer pipeline, the request coalescer, the gadget layer and WoP-PBS; capi_multi.cpp: multi-device
-// contexts; capi_u32.cpp, capi_u128.cpp: the other torus widths; capi_ingress.cpp: compressed ciphertext
-// sources).  What crosses a subsystem's boundary is declared here, in namespace tfhe_mi355::capi; what one file
-// alone uses stays in its anonymous namespace.
+// split by subsystem (capi.cpp: errors, contexts, key transactions and key uploads; capi_pbs.cpp: the kernel-form
+// policy, scratch sizes, launchers and entry points of the u64 PBS and keyswitch family; capi_pipeline.cpp: the
+// host-pointer pipeline and the request coalescer; capi_gadget.cpp: packing keyswitch, products, GGSW nodes and
+// vertical packing; capi_wopbs.cpp: the bootstrapped half of WoP-PBS; capi_multi.cpp: multi-device contexts;
+// capi_u32.cpp, capi_u128.cpp: the other torus widths; capi_ingress.cpp: compressed ciphertext sources).  What
+// crosses a subsystem's boundary is declared here, in namespace tfhe_mi355::capi; what one file alone uses stays
+// in its anonymous namespace.
 // Included by those files only, never by a .hip file or by engine.h.
 #pragma once
 
@@ -434,18 +436,21 @@ struct HostCall {
 
 // ---- functions that cross files ------------------------------------------------------------------
 // capi.cpp
-bool ks_mfma_disabled();  // TFHE_MI355_KS_NO_MFMA, read once
 void require_width64(const TfheMi355Context *c);
 void require_width32(const TfheMi355Context *c);
 void require_fbsk(TfheMi355Context *c);
 void require_ksk(TfheMi355Context *c);
-void require_scratch(size_t have, size_t need);
-void validate_lut_indexes(const uint32_t *idx, size_t count, size_t lut_count);
 void validate_parameters(const TfheMi355Parameters &p);
 TfheMi355Context *create_single(const TfheMi355Parameters &p, int device);
 void abi(int rc);
+
+// capi_pbs.cpp: the u64 PBS and keyswitch family
+bool ks_mfma_disabled();  // TFHE_MI355_KS_NO_MFMA, read once
+void require_scratch(size_t have, size_t need);
+void validate_lut_indexes(const uint32_t *idx, size_t count, size_t lut_count);
 bool is_large(const TfheMi355Context *c);
 size_t large_chunk(const TfheMi355Context *c);
+size_t quad_max(const TfheMi355Context *c);
 size_t pbs_scratch_bytes(const TfheMi355Context *c, size_t count);
 size_t ks_scratch_bytes(const TfheMi355Context *c, size_t count);
 size_t ks_pbs_scratch_bytes(const TfheMi355Context *c, size_t count);
@@ -462,8 +467,13 @@ void launch_ks_pbs_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_ou
 void launch_pbs_ks_dev(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, const uint64_t *d_luts,
                        size_t lut_count, const uint32_t *d_idx, size_t count, void *scratch, size_t scratch_bytes,
                        hipStream_t s);
+// adapters of launch_pbs_dev and launch_ks_dev to ChunkLaunch (below)
+void chunk_pbs(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *l, size_t lc, const uint32_t *x,
+               size_t n, void *sc, size_t sb, hipStream_t s);
+void chunk_ks(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *, size_t, const uint32_t *,
+              size_t n, void *sc, size_t sb, hipStream_t s);
 
-// capi.cpp: the host-pointer pipeline and the request coalescer
+// capi_pipeline.cpp: the host-pointer pipeline and the request coalescer
 using ChunkLaunch = void (*)(TfheMi355Context *c, const uint64_t *d_in, uint64_t *d_out, const uint64_t *d_luts,
                              size_t lut_count, const uint32_t *d_idx, size_t count, void *scratch,
                              size_t scratch_bytes, hipStream_t s);
@@ -478,10 +488,6 @@ struct ChunkSource {
 void run_host_pipeline(TfheMi355Context *c, const uint64_t *in, size_t in_words, uint64_t *out, size_t out_words,
                        const uint64_t *luts, size_t lut_words, size_t lut_count, const uint32_t *idx, size_t count,
                        ChunkLaunch launch, ScratchSize scratch_size, const ChunkSource *from = nullptr);
-void chunk_pbs(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *l, size_t lc, const uint32_t *x,
-               size_t n, void *sc, size_t sb, hipStream_t s);
-void chunk_ks(TfheMi355Context *c, const uint64_t *i, uint64_t *o, const uint64_t *, size_t, const uint32_t *,
-              size_t n, void *sc, size_t sb, hipStream_t s);
 bool coalescible(size_t count);
 void coalesced_call(TfheMi355Context *c, CoalescedOp op, CoalescedReq &r);
 
@@ -495,7 +501,7 @@ void split_rows(TfheMi355Context *m, size_t count, const std::function<int(TfheM
 void multi_key_upload(TfheMi355Context *m, KeyPart part, const std::function<int(TfheMi355Context *)> &first);
 void destroy_multi(TfheMi355Context *m);
 
-// capi.cpp: the gadget layer
+// capi_gadget.cpp: the gadget layer
 struct VpShape {
     uint32_t nt, nr;
 };
@@ -511,7 +517,7 @@ void launch_vertical_packing_dev(TfheMi355Context *c, const double2 *d_fggsw, ui
                                  const uint32_t *d_lut_idx, size_t count, uint64_t *d_lwe_out, void *scratch,
                                  size_t scratch_bytes, hipStream_t s);
 
-// capi.cpp, WoP-PBS: host-pointer form of a call whose items go in chunks through device buffers of the call's
+// capi_wopbs.cpp, WoP-PBS: host-pointer form of a call whose items go in chunks through device buffers of the call's
 // own, on the context's stream; f(d_in, d_out, d_idx, n, d_scratch, scratch_bytes, stream) launches one chunk
 constexpr size_t kWopChunkRows = 4096;  // PBS rows per chunk of the host-pointer forms
 void host_wop_call(TfheMi355Context *ctx, const uint64_t *in, size_t in_words, uint64_t *out, size_t out_words,
